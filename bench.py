@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): exact inner-product top-100 of 4096 fp32 queries against a
 synthetic 1.5M x 768 fp32 KB resident in HBM, on ONE MI355X.  A "step" is one search call over the
 whole batch; inputs are already in HBM when the timed region starts, D/I are written inside it.
-Two exact paths exist and return bit-identical results (checked in every run):
+Two exact paths exist and return bit-identical results (checked in every --full run):
   --mode screened (default): mq_knn_search_screened_f32 = bf16 MFMA screening scan with a provable
       error margin + exact fp32 re-scoring of the survivors (csrc/knn_screen.inc);
   --mode exact_f32: mq_knn_search_f32 = fp32 MFMA scan with the top-k fused (csrc/knn.hip).
-The headline `value` is the selected mode; the other path is timed next to it (`other_exact_path`).
+The headline `value` is the selected mode; with --full the other path is timed next to it (`other_exact_path`).
+
+A plain run sets up, warms up, times the --steps steps and prints the line (`value`, `ms_per_step`, the roofline of the timed
+launches).  Everything else -- the other exact path, the small-batch and big-k legs, the sustained MFMA ceiling, the screen
+statistics, the encoder and call-surface figures, the CPU baselines, and with several ranks the step breakdown and the strong
+scaling run -- needs --full.  --dump-outputs DIR writes what the last timed step returned (D.npy, I.npy).
 
 N > 1 (BASELINE configs[4]: 12M x 768 over 8 GPUs, 16k queries): the KB is
 row-sharded, one 1.5M-row shard per rank (weak scaling: per-GPU work fixed), 16,384 replicated
@@ -20,8 +25,8 @@ rank's shard record, ONE RCCL all-gather of the records (async, overlapping the 
 merge on every rank}.  `value` counts the units all ranks processed: one unit = one query's exact
 top-100 over one 1.5M x 768 shard (the BASELINE metric's unit), so value = N * nq * K / t; the
 end-to-end rate of finished queries over the N x 1.5M KB is `global_queries_per_s`.  Rank 0 also
-reports the per-chunk scan / all-gather / merge times of an un-overlapped pass, the RCCL rank count
-it saw, and the same search with the TOTAL KB fixed at 1.5M rows (strong scaling).
+reports the RCCL rank count it saw and, with --full, the per-chunk scan / all-gather / merge times of an
+un-overlapped pass and the same search with the TOTAL KB fixed at 1.5M rows (strong scaling).
 
 `python bench.py --gpus N` without WORLD_SIZE in the environment starts the N ranks itself (a
 `torch.distributed.run` child process, before this process touches any GPU) and relays their line.
@@ -47,6 +52,7 @@ TOPK = 100
 PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense f32-input MFMA peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 MFMA peak
 PEAK_HBM_GBPS = 8000.0
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def parse():
@@ -62,13 +68,39 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-encoders", action="store_true", help="skip the secondary encoder throughput figures")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed headline steps (no CPU baseline, encoders, other path, small-batch / big-k legs): the command "
-                         "tools/profile_round.sh profiles, so that the rocprofv3 average of the scan kernel is the headline launch's")
+                    help="with --full: no CPU baseline, encoders, other path, small-batch / big-k legs (a run without --full has none "
+                         "of them either): the command tools/profile_round.sh profiles, so that the rocprofv3 average of the scan "
+                         "kernel is the headline launch's")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample duration")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline steps (the options above select among these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/D.npy (float32 scores) and "
+                                                          "DIR/I.npy (ids as float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.headline_only = True
     if args.headline_only:
         args.no_cpu_baseline = args.no_encoders = args.no_other_path = True
     return args
+
+
+def dump_outputs(path, D, I):
+    """What the timed path returned in its last step: D [nq, k] float32 and I [nq, k] (int64 ids, written as float64: exact
+    below 2^53).  Above DUMP_BYTES in all, a fixed seeded sample of query rows, sorted, whose row numbers go to rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    D = D.cpu().numpy().astype(np.float32)
+    I = I.cpu().numpy().astype(np.float64)
+    nq, k = D.shape
+    per_row = k * (4 + 8) + 8
+    keep = (DUMP_BYTES - 4096) // per_row  # (room for the three .npy headers)
+    if nq > keep:
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        D, I = D[rows], I[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "D.npy"), D)
+    np.save(os.path.join(path, "I.npy"), I)
 
 
 def build_shard(idx, rows, seed, device):
@@ -477,8 +509,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *out)
 
-    if multi:
+    scan_ms = breakdown = None
+    if multi and args.full:
         # un-overlapped pass: per 4096-query chunk, HIP events around the scan kernel (through the C ABI), the collective
         # and the merge -- what the pipelined step hides is the difference to `ms_per_step`
         from viquae_amd.sharded import record_layout, _record_views, _hip_merge_records
@@ -514,13 +549,12 @@ def main():
         t = torch.tensor([breakdown["all_gather_ms"], breakdown["merge_ms"], breakdown["scan_call_ms"]], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         breakdown["max_over_ranks"] = {"all_gather_ms": round(float(t[0]), 3), "merge_ms": round(float(t[1]), 3), "scan_call_ms": round(float(t[2]), 3)}
-    else:
+    elif not multi:
         scan_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps
-        breakdown = None
 
     # strong scaling ("N total fixed"): the SAME 1.5M-row KB cut into `world` shards
     fixed_total = None
-    if world > 1:
+    if world > 1 and args.full:
         from viquae_amd.sharded import shard_bounds
         lo, hi = shard_bounds(rows, world, rank)
         small = MI355XFlatIndex(device=local_rank, string_factory="Flat", metric_type=0, id_offset=lo, screen=mode == "screened")
@@ -653,7 +687,6 @@ def main():
         units = world * nq * args.steps
         value = units / elapsed
         flops = 2.0 * nqc * rows * DIM  # algorithmic FLOPs of one scan launch (2.304 GFLOP/query)
-        achieved = flops / (scan_ms * 1e-3) / 1e12
         info = (ctypes_i64 * 8)()
         lib.mq_knn_launch_info(rows, DIM, nqc, k, info)
         workload = (f"{rows}x{DIM} fp32 KB per GPU, {nq} queries, exact IP top-{k}" if not multi else
@@ -695,7 +728,10 @@ def main():
                                 "lds_bytes": int(info[7] if mode == "screened" else info[2]),
                                 "query_tiles": int(info[3]), "kb_slabs": int(info[4]), "kb_chunks": int(info[5])},
             },
-            "roofline": {
+        }
+        if scan_ms is not None:  # several ranks: the scan kernel is timed in the --full breakdown pass only
+            achieved = flops / (scan_ms * 1e-3) / 1e12
+            rec["roofline"] = {
                 "bound": "mfma",
                 "kernel": kernel,
                 "achieved": round(achieved, 2),
@@ -710,9 +746,8 @@ def main():
                 "hbm_frac_at_one_pass": round(alg_bytes / (scan_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4),
                 "traffic": traffic[0],
                 "traffic_from_profile": traffic[1],
-            },
-        }
-        if world == 1 and mode == "screened":
+            }
+        if world == 1 and mode == "screened" and args.full:
             try:
                 rec["roofline"]["sustained_mfma_ceiling"] = mfma_ceiling(device, stream, achieved)
             except Exception as e:  # a diagnostic, never a reason to lose the line
@@ -723,7 +758,7 @@ def main():
             rec["config"]["step_breakdown_ms"] = breakdown
         if fixed_total is not None:
             rec["config"]["fixed_total_kb"] = fixed_total
-        if mode == "screened":
+        if mode == "screened" and args.full:
             local._ws, keep = ws, local._ws
             st = local.screen_stats(nqc, k)
             local._ws = keep

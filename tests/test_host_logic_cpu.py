@@ -306,6 +306,32 @@ def test_bench_gpus_n_starts_its_own_ranks_before_touching_a_gpu(monkeypatch):
     assert "only 2 GPU" in str(e.value.code) and not seen
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_size_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: D as float32, the int64 ids as float64; above the size cap the same seeded, sorted
+    sample of query rows every time (rows.npy holds their numbers) and no more bytes than the cap."""
+    import importlib
+    import torch
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(3)
+    D = torch.from_numpy(rng.standard_normal((300, 7)).astype(np.float32))
+    I = torch.from_numpy(rng.integers(0, 1 << 40, (300, 7)))
+    bench.dump_outputs(str(tmp_path / "all"), D, I)
+    assert sorted(os.listdir(tmp_path / "all")) == ["D.npy", "I.npy"]
+    Dg, Ig = np.load(tmp_path / "all" / "D.npy"), np.load(tmp_path / "all" / "I.npy")
+    assert Dg.dtype == np.float32 and Ig.dtype == np.float64
+    assert np.array_equal(Dg, D.numpy()) and np.array_equal(Ig.astype(np.int64), I.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 50 * (7 * 12 + 8))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), D, I)
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 50 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "D.npy"), D.numpy()[r])
+    assert np.array_equal(np.load(tmp_path / "a" / "I.npy").astype(np.int64), I.numpy()[r])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES
+
+
 def test_faiss_file_writer_round_trips_through_the_reader_and_matches_the_hand_assembled_layout(tmp_path):
     """save() of a "*.faiss" / "*.index" path (or format="faiss") writes what faiss.write_index writes for IndexFlat /
     IndexPreTransform + NormalizationTransform + IndexFlat (meerqat/ir/search.py:247-248: save_faiss_index): byte-identical

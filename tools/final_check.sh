@@ -1,15 +1,17 @@
 #!/bin/bash
-# Round-end check on a GPU box: the driver's own sequence (GPU tests, smoke) + the default bench line.
+# Check on an MI355X: the GPU tests, smoke() and the full bench line, logs under [outdir] (default out/).
 cd ${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-mkdir -p gpurun_out
-python -m pytest tests/ -q -m gpu 2>&1 | grep -E "passed|failed|rror" | tail -6 > gpurun_out/final_gpu_tests.log
-cat gpurun_out/final_gpu_tests.log
+O=${1:-out}
+mkdir -p $O
+python -m pytest tests/ -q -m gpu 2>&1 | grep -E "passed|failed|rror" | tail -6 > $O/final_gpu_tests.log
+cat $O/final_gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -i smoke
-python bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err
-tail -2 gpurun_out/final_bench.err
-python - <<'PY'
+python bench.py --full > $O/final_bench.json 2> $O/final_bench.err
+tail -2 $O/final_bench.err
+python - "$O/final_bench.json" <<'PY'
 import json
-d = json.load(open("gpurun_out/final_bench.json"))
+import sys
+d = json.load(open(sys.argv[1]))
 print({k: d[k] for k in ("value", "ms_per_step", "n_gpus", "dtype")}, d["roofline"]["frac"], d["roofline"]["kernel_ms"])
 cb = d["cpu_baseline"]; print("cpu", cb["value"], cb["cores"], cb["kind"]); print(cb["sample"][:700]); print(cb.get("encoders"))
 s = d["secondary"]

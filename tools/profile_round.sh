@@ -29,6 +29,6 @@ timeout 400 rocprofv3 --pmc WRITE_SIZE -d $O/nq256_write --output-format csv -- 
 timeout 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT -d $O/nq256_sq --output-format csv -- $S > $O/nq256_sq.log 2>&1
 timeout 400 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $O/nq256_tcc --output-format csv -- $S > $O/nq256_tcc.log 2>&1
 cd $R
-timeout 900 python3 bench.py > $O/bench.json 2> $O/bench.err
-timeout 600 python3 bench.py --mode exact_f32 --no-encoders --no-other-path > $O/bench_exact.json 2>> $O/bench.err
+timeout 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err
+timeout 600 python3 bench.py --full --mode exact_f32 --no-encoders --no-other-path > $O/bench_exact.json 2>> $O/bench.err
 ls $O
