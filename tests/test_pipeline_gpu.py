@@ -110,13 +110,10 @@ def test_pipelined_text_embed_with_a_tokenizer_the_fast_path_declines(tmp_path, 
         assert np.array_equal(outs[0], outs[1])
 
 
-def test_pipelined_image_embed_is_identical_to_the_serial_embed(tmp_path, monkeypatch):
-    import datasets
-    from PIL import Image
+def _image_job_kwargs(tmp_path, batch_size):
+    """A seeded tiny CLIP checkpoint with its preprocessor config -> the keyword arguments of image.embedding.dataset_embed."""
     from safetensors.torch import save_file
     from oracle import encoders as oe
-    from viquae_amd.data import loading
-    from viquae_amd.image import embedding as IE
     cfg = oe.CLIP_TINY
     state = oe.seeded_state(oe.clip_vision_param_shapes(cfg), 4)
     mdir = tmp_path / "clip"
@@ -126,6 +123,20 @@ def test_pipelined_image_embed_is_identical_to_the_serial_embed(tmp_path, monkey
     S = cfg["image_size"]
     (mdir / "preprocessor_config.json").write_text(json.dumps({"feature_extractor_type": "CLIPFeatureExtractor", "size": S, "crop_size": S,
                                                                "resample": 3, "do_resize": True, "do_center_crop": True, "do_normalize": True}))
+    return dict(map_kwargs={"batch_size": batch_size}, save_as="clip", call="get_image_features",
+                model_kwargs={"type": "transformers", "class_name": "CLIPModel", "pretrained_model_name_or_path": str(mdir)},
+                transform_kwargs={"class_name": "CLIPFeatureExtractor", "pretrained_model_name_or_path": str(mdir)})
+
+
+def test_pipelined_image_embed_is_identical_to_the_serial_embed(tmp_path, monkeypatch):
+    import datasets
+    from PIL import Image
+    from oracle import encoders as oe
+    from viquae_amd.data import loading
+    from viquae_amd.image import embedding as IE
+    cfg = oe.CLIP_TINY
+    S = cfg["image_size"]
+    kw = _image_job_kwargs(tmp_path, 8)
     rng = np.random.default_rng(3)
     monkeypatch.setattr(loading, "IMAGE_PATH", tmp_path)
     names = []
@@ -141,9 +152,6 @@ def test_pipelined_image_embed_is_identical_to_the_serial_embed(tmp_path, monkey
     (tmp_path / "cut.jpg").write_bytes(data[: len(data) // 2])
     names[30] = "cut.jpg"
     datasets.Dataset.from_dict({"image": names, "id": list(range(45))}).save_to_disk(str(tmp_path / "ds"))
-    kw = dict(map_kwargs={"batch_size": 8}, save_as="clip", call="get_image_features",
-              model_kwargs={"type": "transformers", "class_name": "CLIPModel", "pretrained_model_name_or_path": str(mdir)},
-              transform_kwargs={"class_name": "CLIPFeatureExtractor", "pretrained_model_name_or_path": str(mdir)})
     outs = []
     # serial embed | pipeline with forked decode processes writing into the shared pinned slots (the default; `processes`
     # sets their number) | pipeline with decode threads
@@ -165,3 +173,37 @@ def test_pipelined_image_embed_is_identical_to_the_serial_embed(tmp_path, monkey
         a = np.asarray([v for v in outs[0] if v is not None], dtype=np.float32)
         b = np.asarray([v for v in o if v is not None], dtype=np.float32)
         assert a.shape == (41, cfg["projection_dim"]) and np.array_equal(a, b)
+
+
+def test_pipelined_image_embed_decodes_a_batch_larger_than_the_slots_in_threads(tmp_path, monkeypatch):
+    """A batch whose decoded RGB bytes exceed the decode workers' staging slot (images larger than the slots were sized for)
+    is decoded by the pipeline's threads, the batches that fit go through the workers' shared slots: the output is the
+    serial embed's all the same, bit for bit."""
+    import datasets
+    from PIL import Image
+    from viquae_amd.data import loading
+    from viquae_amd.image import decode_pool, embedding as IE
+    slot = 256 << 10
+    monkeypatch.setattr(decode_pool, "slot_bytes", lambda batch_size: slot)
+    monkeypatch.setattr(loading, "IMAGE_PATH", tmp_path)
+    kw = _image_job_kwargs(tmp_path, 4)
+    rng = np.random.default_rng(5)
+    sizes = [(80, 96), (96, 80), (72, 100), (90, 90), (88, 70), (320, 330), (100, 64), (70, 70), (64, 99), (81, 77), (99, 66)]
+    names = []
+    for i, (h, w) in enumerate(sizes):
+        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(tmp_path / f"im{i}.png")
+        names.append(f"im{i}.png")
+    # the packed RGB bytes of each batch of 4 (16-byte aligned rows, like the pipeline's plan): one batch overflows, the others fit
+    need = [sum((h * w * 3 + 15) // 16 * 16 for h, w in sizes[b:b + 4]) for b in range(0, len(sizes), 4)]
+    assert need[1] > slot and need[0] <= slot and need[2] <= slot
+    datasets.Dataset.from_dict({"image": names, "id": list(range(len(names)))}).save_to_disk(str(tmp_path / "ds"))
+    outs = []
+    for flag in ("0", "1"):
+        monkeypatch.setenv("MQ_EMBED_PIPELINE", flag)
+        ds = IE.dataset_embed(str(tmp_path / "ds"), output_path=str(tmp_path / f"out{flag}"),
+                               processes=2 if flag == "1" else None, **kw)
+        outs.append(np.asarray(ds["clip"], dtype=np.float32))
+        st = IE.dataset_embed.last_pipeline_stats
+        assert (st is not None) == (flag == "1")
+    assert st["batches"] == 3 and st["decode"].startswith("2 processes")
+    assert outs[0].shape == (len(sizes), 64) and np.array_equal(outs[0], outs[1])

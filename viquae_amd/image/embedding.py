@@ -64,9 +64,8 @@ def dataset_embed(dataset_path, map_kwargs={}, model_kwargs={}, transform_kwargs
         keep_columns = set(keep_columns)
         dataset = dataset.remove_columns([c for c in dataset.column_names if c not in keep_columns])
     # the decode workers of the pipeline are forked FIRST, while this process owns no page-locked memory (decode_pool.py)
-    from .decode_pool import early_pool
-    from ..pipeline import _map_batch_size
-    workers = early_pool(processes, _map_batch_size(map_kwargs)) if _map_batch_size(map_kwargs) is not None else None
+    from ..pipeline import early_decode_pool, image_pipeline_or_none, map_encode_job
+    workers = early_decode_pool(processes, map_kwargs)
     fn_kwargs.update(get_model_and_transform(model_kwargs=model_kwargs, transform_kwargs=transform_kwargs))
     from ..ir.embedding import _rank_shard, _save_rank_shards, process_rank_and_world
     rank, world = process_rank_and_world()
@@ -75,24 +74,12 @@ def dataset_embed(dataset_path, map_kwargs={}, model_kwargs={}, transform_kwargs
     # decode / pack / H2D / device-side resize of batch i + 1 behind the CLIP forward of batch i (viquae_amd/pipeline.py).
     # `processes` (the reference's pool size) then sets the number of DECODE processes, which write the RGB bytes straight
     # into a shared page-locked staging buffer instead of pickling arrays back (viquae_amd/image/decode_pool.py).
-    from ..pipeline import image_pipeline_or_none
+    from ..utils import job_fingerprint
     pipe = image_pipeline_or_none(dataset, map_kwargs, decode_procs=processes, decode_pool=workers, **fn_kwargs)
-    if pipe is None and workers is not None:
-        workers.close()
-    if pipe is not None:
-        map_kwargs = dict(map_kwargs)
-        if "new_fingerprint" not in map_kwargs:  # see viquae_amd/ir/embedding.py: never pickle the pipeline (model + column) for a hash
-            from ..utils import job_fingerprint
-            map_kwargs["new_fingerprint"] = job_fingerprint(dataset, "image.embedding.dataset_embed", **fn_kwargs)
-        try:
-            dataset = dataset.map(pipe.embed, batched=True, with_indices=True, **map_kwargs)
-        finally:
-            pipe.close()
-            dataset_embed.last_pipeline_stats = dict(pipe.stats)
-    else:
-        dataset_embed.last_pipeline_stats = None
+    if pipe is None:
         fn_kwargs["pool"] = None if processes is None else Pool(processes=processes)
-        dataset = dataset.map(embed, batched=True, fn_kwargs=fn_kwargs, **map_kwargs)
+    dataset = map_encode_job(dataset_embed, dataset, map_kwargs, pipe, embed, fn_kwargs,
+                             lambda: job_fingerprint(dataset, "image.embedding.dataset_embed", **fn_kwargs))
     if world > 1:
         return _save_rank_shards(dataset, dataset_path, output_path, rank, world)
     return _save(dataset, dataset_path, output_path)

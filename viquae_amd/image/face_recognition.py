@@ -215,32 +215,22 @@ def dataset_compute_face_embedding(dataset_path, map_kwargs={}, pretrained_kwarg
     ArcFace forward of batch i); ``MQ_EMBED_PIPELINE=0`` maps the serial ``compute_face_embedding``."""
     from datasets import load_from_disk
     from .embedding import _save
-    from .decode_pool import early_pool
-    from ..pipeline import _map_batch_size, face_pipeline_or_none
+    from ..pipeline import early_decode_pool, face_pipeline_or_none, map_encode_job
     map_kwargs, fn_kwargs = dict(map_kwargs), dict(fn_kwargs)
     for k in ("max_n_faces", "image_key"):
         if k in map_kwargs:
             fn_kwargs.setdefault(k, map_kwargs.pop(k))
     dataset = load_from_disk(dataset_path)
     # the decode workers are forked FIRST, while this process owns no page-locked memory (decode_pool.py)
-    workers = early_pool(None, _map_batch_size(map_kwargs)) if _map_batch_size(map_kwargs) is not None else None
+    workers = early_decode_pool(None, map_kwargs)
     model = from_pretrained(**pretrained_kwargs)
     pipe = face_pipeline_or_none(dataset, map_kwargs, model=model, decode_pool=workers, **fn_kwargs)
-    if pipe is None and workers is not None:
-        workers.close()
-    if "new_fingerprint" not in map_kwargs:  # never pickle the model for a hash
+    if "new_fingerprint" not in map_kwargs:  # never pickle the model for a hash (on both paths)
         from datasets.fingerprint import generate_random_fingerprint
         map_kwargs["new_fingerprint"] = generate_random_fingerprint()
-    if pipe is not None:
-        try:
-            dataset = dataset.map(pipe.embed, batched=True, with_indices=True, **map_kwargs)
-        finally:
-            pipe.close()
-            dataset_compute_face_embedding.last_pipeline_stats = dict(pipe.stats)
-    else:
-        dataset_compute_face_embedding.last_pipeline_stats = None
+    if pipe is None:
         fn_kwargs = dict(fn_kwargs, model=model, preprocessor=get_pil_preprocessor(), tform=SimilarityTransform())
-        dataset = dataset.map(compute_face_embedding, batched=True, fn_kwargs=fn_kwargs, **map_kwargs)
+    dataset = map_encode_job(dataset_compute_face_embedding, dataset, map_kwargs, pipe, compute_face_embedding, fn_kwargs)
     return _save(dataset, dataset_path, dataset_path)
 
 

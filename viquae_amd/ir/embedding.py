@@ -171,27 +171,14 @@ def dataset_embed(dataset_path, map_kwargs={}, output_path=None, keep_columns=No
         dataset = _rank_shard(dataset, rank, world)
     # Dataset.map stays the driver.  For the plain job (texts = batch[key] as they are, a CUDA model) the function it calls is
     # a software-pipelined embed: tokenisation / pinned staging / H2D of batch i + 1 and the Arrow write of batch i - 1 overlap
-    # the forward of batch i (viquae_amd/pipeline.py); everything else maps the serial `embed` below
-    from ..pipeline import text_pipeline_or_none
+    # the forward of batch i (viquae_amd/pipeline.py); everything else maps the serial `embed` below.  The pipelined map is named
+    # by a deterministic fingerprint of the JOB (utils.job_fingerprint: input fingerprint, model checksums, tokenizer identity,
+    # keyword arguments), so that an identical second run hits the map cache like the reference's `dataset.map(embed, ...)` does.
+    from ..pipeline import map_encode_job, text_pipeline_or_none
+    from ..utils import job_fingerprint
     pipe = text_pipeline_or_none(dataset, map_kwargs, **fn_kwargs)
-    if pipe is not None:
-        # `datasets` fingerprints the mapped function by pickling it: for the bound method of the pipeline that is the model's
-        # weights AND the whole text column (seconds and gigabytes for a passage KB), and the hash would depend on run state.
-        # A deterministic fingerprint of the JOB instead (utils.job_fingerprint: input fingerprint, model checksums, tokenizer
-        # identity, keyword arguments), so that an identical second run hits the map cache like the reference's
-        # `dataset.map(embed, fn_kwargs=...)` does -- unless the caller names one.
-        map_kwargs = dict(map_kwargs)
-        if "new_fingerprint" not in map_kwargs:
-            from ..utils import job_fingerprint
-            map_kwargs["new_fingerprint"] = job_fingerprint(dataset, "ir.embedding.dataset_embed", **fn_kwargs)
-        try:
-            dataset = dataset.map(pipe.embed, batched=True, with_indices=True, **map_kwargs)
-        finally:
-            pipe.close()
-            dataset_embed.last_pipeline_stats = dict(pipe.stats)
-    else:
-        dataset_embed.last_pipeline_stats = None
-        dataset = dataset.map(embed, batched=True, fn_kwargs=fn_kwargs, **map_kwargs)
+    dataset = map_encode_job(dataset_embed, dataset, map_kwargs, pipe, embed, fn_kwargs,
+                             lambda: job_fingerprint(dataset, "ir.embedding.dataset_embed", **fn_kwargs))
     if world > 1:
         return _save_rank_shards(dataset, dataset_path, output_path, rank, world)
     return _save(dataset, dataset_path, output_path)

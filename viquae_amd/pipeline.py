@@ -22,6 +22,7 @@ import os
 import queue
 import threading
 import time
+import types
 
 import numpy as np
 import torch
@@ -228,31 +229,97 @@ def _arrow_strings(dataset, key):
     return col
 
 
-class TextEmbedPipeline:
+def model_device(model):
+    """The device of the model's first parameter, else of its first buffer (models that keep their weights as buffers only, like
+    the ArcFace port); None for an object with neither."""
+    first = next(iter(model.parameters()), None) if hasattr(model, "parameters") else None
+    if first is None and hasattr(model, "buffers"):
+        first = next(iter(model.buffers()), None)
+    return None if first is None else first.device
+
+
+class _EncodeJob:
+    """The skeleton of the three encode jobs: batch bounds, device, streams, pinned output ring, :class:`Lookahead`, ``embed``.
+    A job sets its own state, then calls ``_EncodeJob.__init__`` (the worker starts on batch 0 at once), and implements
+    ``_prepare(j)`` (worker thread) -> dict(names = ``batch[key]``, event = side-stream event of the inputs or None when there
+    is nothing to run, tensors = device tensors the forward reads, info = what ``_result`` needs, ...), ``_forward(p)`` -> the
+    device result, one row per output row, and ``_result(batch, found, info)`` -> what ``Dataset.map`` gets back."""
+
+    def __init__(self, dataset, model, key, batch_size, stats, depth=2):
+        self.model, self.key = model, key
+        n = len(dataset)
+        self.bounds = [(s, min(s + batch_size, n)) for s in range(0, n, batch_size)]
+        self.device = model_device(model)
+        self.main = torch.cuda.current_stream(self.device)
+        self.side = torch.cuda.Stream(device=self.device)
+        self.out_ring = _PinnedRing(3)
+        self.stats = {"batches": 0, "prepare_s": 0.0, "launch_s": 0.0, "wait_result_s": 0.0, **stats}
+        self.look = Lookahead(len(self.bounds), self._prepare, self._launch, depth=depth)
+
+    # ---- caller's thread -------------------------------------------------------------------------------------------
+    def _launch(self, p):
+        """Batch j's forward on the compute stream behind the worker's event, its float32 result copied to pinned memory."""
+        t0 = time.perf_counter()
+        extra = (p["names"], p["info"])
+        if p["event"] is None:
+            return _Handle(None, torch.empty((0, 1)), 0, extra=extra)
+        with torch.cuda.device(self.device):
+            self.main.wait_event(p["event"])
+            for t in p["tensors"]:
+                t.record_stream(self.main)
+            with torch.no_grad():
+                out = self._forward(p)
+            out = out.to(torch.float32).contiguous()
+            slot, buf = self.out_ring.take(out.numel() * 4)
+            pinned = buf[: out.numel() * 4].view(torch.float32).view(out.shape)
+            pinned.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.main)
+            self.out_ring.events[slot] = ev
+        self.stats["launch_s"] += time.perf_counter() - t0
+        return _Handle(ev, pinned, out.shape[0], extra=extra)
+
+    def embed(self, batch, indices):
+        """The function ``Dataset.map`` calls (batched, with_indices) for THIS batch."""
+        i = self.stats["batches"]
+        s, e = self.bounds[i] if i < len(self.bounds) else (-1, -1)
+        if len(indices) != e - s or int(indices[0]) != s or int(indices[-1]) != e - 1:
+            raise RuntimeError("Dataset.map handed over batches in another order than the prefetcher prepared them "
+                               f"(batch {i}: rows {indices[0]}..{indices[-1]}, expected {s}..{e - 1}); set MQ_EMBED_PIPELINE=0")
+        t0 = time.perf_counter()
+        found, (names, info) = self.look.step(i)
+        self.stats["wait_result_s"] += time.perf_counter() - t0
+        if names != batch[self.key]:
+            raise RuntimeError(f"the prefetched '{self.key}' of batch {i} differ from what Dataset.map decoded; set MQ_EMBED_PIPELINE=0")
+        self.stats["batches"] = i + 1
+        self.stats.setdefault("returned_at", []).append(time.perf_counter())  # per batch: lets a caller separate start-up from pace
+        return self._result(batch, found, info)
+
+    def close(self):
+        self.stats["wait_prepared_s"] = self.look.wait_prepared_s
+        self.look.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# text
+# ----------------------------------------------------------------------------------------------------------------------
+class TextEmbedPipeline(_EncodeJob):
     """``embed`` for ``Dataset.map(..., batched=True, with_indices=True)`` with the host stages of batch i + 1 (Arrow ->
     str, tokenisation, pinned staging, H2D, packed-forward plan) hidden behind the forward of batch i.  Plain passages /
     questions only (no query expansion, no KB features, no per-layer dump): see :func:`text_pipeline_or_none`."""
 
     def __init__(self, dataset, model, tokenizer, tokenization_kwargs, key, save_as, output_key, forward_kwargs, call, batch_size,
                  depth=2):
-        self.model, self.key, self.save_as, self.output_key = model, key, save_as, output_key
+        self.save_as, self.output_key = save_as, output_key
         self.forward_kwargs, self.call = dict(forward_kwargs or {}), call
         self.tokenizer, self.tokenization_kwargs = tokenizer, dict(tokenization_kwargs or {})
         self.column = _arrow_strings(dataset, key)
-        n = len(dataset)
-        self.bounds = [(s, min(s + batch_size, n)) for s in range(0, n, batch_size)]
-        self.device = next(iter(model.parameters()), None)
-        self.device = (self.device if self.device is not None else next(iter(model.buffers()))).device
-        self.main = torch.cuda.current_stream(self.device)
-        self.side = torch.cuda.Stream(device=self.device)
         self.fast = FastBatchTokenizer(tokenizer, self.tokenization_kwargs)
         self._checked = False
         self.use_plan = bool(getattr(model, "supports_pack_plan", False)) and call is None and not self.fast.left
         self.in_ring = _PinnedRing(depth + 2)
-        self.out_ring = _PinnedRing(3)
-        self.stats = {"batches": 0, "tokenize_s": 0.0, "prepare_s": 0.0, "launch_s": 0.0, "wait_result_s": 0.0,
-                      "fast_tokenizer": None, "pack_plan": self.use_plan}
-        self.look = Lookahead(len(self.bounds), self._prepare, self._launch, depth=depth)
+        super().__init__(dataset, model, key, batch_size, {"tokenize_s": 0.0, "fast_tokenizer": None, "pack_plan": self.use_plan},
+                         depth=depth)
 
     # ---- worker thread ---------------------------------------------------------------------------------------------
     def _prepare(self, j):
@@ -307,58 +374,24 @@ class TextEmbedPipeline:
             ev = torch.cuda.Event()
             ev.record(self.side)
         self.in_ring.events[slot] = ev
+        used = list(inputs.values())
+        if plan is not None:
+            keep, pos, cu, classes, cls_rows = plan
+            used += [keep, pos, cu, cls_rows] + [c[0] for c in classes]
         self.stats["prepare_s"] += time.perf_counter() - t0
-        return {"texts": texts, "inputs": inputs, "plan": plan, "event": ev, "rows": len(texts)}
+        return {"names": texts, "event": ev, "tensors": used, "info": None, "inputs": inputs, "plan": plan}
 
     # ---- caller's thread -------------------------------------------------------------------------------------------
-    def _launch(self, p):
-        t0 = time.perf_counter()
-        with torch.cuda.device(self.device):
-            self.main.wait_event(p["event"])
-            for t in p["inputs"].values():
-                t.record_stream(self.main)
-            if p["plan"] is not None:
-                keep, pos, cu, classes, cls_rows = p["plan"]
-                for t in [keep, pos, cu, cls_rows] + [c[0] for c in classes]:
-                    t.record_stream(self.main)
-            method = self.model if self.call is None else getattr(self.model, self.call)
-            kw = dict(self.forward_kwargs)
-            if p["plan"] is not None:
-                kw["pack_plan"] = p["plan"]
-            with torch.no_grad():
-                outputs = method(**p["inputs"], **kw)
-            output = select_output(outputs, self.output_key)
-            output = output.to(torch.float32) if output.dtype != torch.float32 else output
-            output = output.contiguous()
-            slot, buf = self.out_ring.take(output.numel() * 4)
-            pinned = buf[: output.numel() * 4].view(torch.float32).view(output.shape)
-            pinned.copy_(output, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.out_ring.events[slot] = ev
-        self.stats["launch_s"] += time.perf_counter() - t0
-        return _Handle(ev, pinned, p["rows"], extra=p["texts"])
+    def _forward(self, p):
+        method = self.model if self.call is None else getattr(self.model, self.call)
+        kw = dict(self.forward_kwargs)
+        if p["plan"] is not None:
+            kw["pack_plan"] = p["plan"]
+        return select_output(method(**p["inputs"], **kw), self.output_key)
 
-    def embed(self, batch, indices):
-        """The function ``Dataset.map`` calls (batched, with_indices): ``batch[save_as]`` = float32 [B, H] of THIS batch."""
-        i = self.stats["batches"]
-        s, e = self.bounds[i] if i < len(self.bounds) else (-1, -1)
-        if len(indices) != e - s or int(indices[0]) != s or int(indices[-1]) != e - 1:
-            raise RuntimeError("Dataset.map handed over batches in another order than the prefetcher prepared them "
-                               f"(batch {i}: rows {indices[0]}..{indices[-1]}, expected {s}..{e - 1}); set MQ_EMBED_PIPELINE=0")
-        t0 = time.perf_counter()
-        out, texts = self.look.step(i)
-        self.stats["wait_result_s"] += time.perf_counter() - t0
-        if texts != batch[self.key]:
-            raise RuntimeError(f"the prefetched texts of batch {i} differ from what Dataset.map decoded; set MQ_EMBED_PIPELINE=0")
-        self.stats["batches"] = i + 1
-        self.stats.setdefault("returned_at", []).append(time.perf_counter())  # per batch: lets a caller separate start-up from pace
-        batch[self.save_as] = out
+    def _result(self, batch, found, info):
+        batch[self.save_as] = found   # float32 [B, H]
         return batch
-
-    def close(self):
-        self.stats["wait_prepared_s"] = self.look.wait_prepared_s
-        self.look.close()
 
 
 def select_output(outputs, output_key):
@@ -396,49 +429,94 @@ def _map_batch_size(map_kwargs):
     return bs if bs > 0 else None
 
 
+def _job_batch_size(dataset, map_kwargs, model, key, job_ok, decode_pool=None):
+    """The batch size of a job the prefetcher can reproduce ahead of ``Dataset.map`` -- ``job_ok`` (the job's own conditions), the
+    pipeline switched on, a CUDA model, a plain ``datasets.Dataset`` walked in order, ``batch[key]`` a string column as it is --
+    else None: the caller then maps the serial function, and the decode workers it forked for the pipeline are closed."""
+    bs = _map_batch_size(map_kwargs)
+    ok = (job_ok and pipeline_enabled() and bs is not None and torch.cuda.is_available() and _plain_dataset(dataset, map_kwargs)
+          and _arrow_strings(dataset, key) is not None)
+    device = model_device(model) if ok else None
+    if device is None or device.type != "cuda":
+        if decode_pool is not None:
+            decode_pool.close()
+        return None
+    return bs
+
+
 def text_pipeline_or_none(dataset, map_kwargs, model=None, tokenizer=None, tokenization_kwargs={}, key="passage",
                           save_as="text_embedding", output_key=None, forward_kwargs={}, layers=None, kb=None, call=None, run=None,
                           qe_predictions_key=None, **other):
-    """A :class:`TextEmbedPipeline` when the job is the plain one the prefetcher can reproduce ahead of ``Dataset.map`` --
-    a CUDA model, a plain ``datasets.Dataset`` walked in order, texts = ``batch[key]`` as they are -- else None (the caller
-    then maps the serial ``embed``)."""
-    if not pipeline_enabled() or other or layers is not None or kb is not None or run is not None or qe_predictions_key is not None:
-        return None
-    if _map_batch_size(map_kwargs) is None or getattr(tokenizer, "truncation_side", "right") != "right":
-        return None  # (the fast tokenizer path truncates on the right like the tokenizer's default; anything else: the serial embed)
-    if model is None or tokenizer is None or not torch.cuda.is_available() or not _plain_dataset(dataset, map_kwargs):
-        return None
+    """A :class:`TextEmbedPipeline` for the plain text job (texts = ``batch[key]`` as they are), else None."""
     from .ir.embedding import is_multimodal
-    if is_multimodal(model) or not isinstance(model, torch.nn.Module):
+    # (the fast tokenizer path truncates on the right like the tokenizer's default; anything else: the serial embed)
+    plain = (not other and layers is None and kb is None and run is None and qe_predictions_key is None and tokenizer is not None
+             and getattr(tokenizer, "truncation_side", "right") == "right" and isinstance(model, torch.nn.Module)
+             and not is_multimodal(model))
+    bs = _job_batch_size(dataset, map_kwargs, model, key, plain)
+    if bs is None:
         return None
-    first = next(iter(model.parameters()), None)
-    first = first if first is not None else next(iter(model.buffers()), None)
-    if first is None or not first.is_cuda or _arrow_strings(dataset, key) is None:
-        return None
-    return TextEmbedPipeline(dataset, model, tokenizer, tokenization_kwargs, key, save_as, output_key, forward_kwargs, call,
-                             _map_batch_size(map_kwargs))
+    return TextEmbedPipeline(dataset, model, tokenizer, tokenization_kwargs, key, save_as, output_key, forward_kwargs, call, bs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# images and faces: the decode workers' shared slots
+# ----------------------------------------------------------------------------------------------------------------------
+def _rgb_plan(sizes):
+    """sizes int64 [n, 2] (h, w) -> (geom int64 [n, 3] = (byte offset, h, w), totals int64 [1] = bytes): the decoded RGB images
+    back to back at 16-byte aligned offsets, the packing of ``mq_image_plan`` and of ``jpeg.plan_layout``'s host-decoded rows."""
+    nbytes = (sizes[:, 0] * sizes[:, 1] * 3 + 15) & ~15
+    geom = np.zeros((len(sizes), 3), dtype=np.int64)
+    geom[1:, 0] = np.cumsum(nbytes)[:-1]
+    geom[:, 1:] = sizes
+    return geom, np.array([nbytes.sum()], dtype=np.int64)
+
+
+def _stage_decode(decode, slot_busy, paths, plan):
+    """Decode-slot staging of an image / face batch: sizes -> ``plan(sizes int64 [n, 2]) -> (geom, totals)`` of the readable
+    files -> JPEG staging areas (``jpeg.plan_layout``) -> a free slot (``slot_busy``: slot -> (event of the copy that last read
+    it, what that copy keeps alive)).  -> (kept, h2d, staging): indices of the readable files, the bytes the batch needs, and
+    None when nothing is readable or the batch does not fit a slot, else (slot, geom, totals, layout, offsets, staged)."""
+    sizes = decode.sizes(paths)
+    kept = [i for i, sz in enumerate(sizes) if sz is not None]
+    if not kept:
+        return kept, 0, None
+    hw = np.array([sizes[i] for i in kept], dtype=np.int64)
+    geom, totals = plan(hw)
+    jrows = {row: decode.last_jpeg[k] for row, k in enumerate(kept) if k in decode.last_jpeg}
+    layout = None
+    if jrows:
+        from .image import jpeg as dj
+        layout = dj.plan_layout(geom, totals, jrows)
+        if int(layout["h2d_bytes"]) > decode.slot_bytes:
+            # coefficients take 2 bytes per sample: a batch of 4:4:4 files can outgrow a slot its RGB bytes fit -- the workers
+            # then decode this batch's files with Pillow, as they do for every other format
+            geom, totals = plan(hw)
+            jrows, layout = {}, None
+    h2d = int(layout["h2d_bytes"] if layout else totals[0])
+    if h2d > decode.slot_bytes:
+        return kept, h2d, None
+    slot = decode.take_slot()
+    busy = slot_busy.pop(slot, None)
+    if busy is not None:      # the copy that last read this slot (two batches ago) must be over before it is rewritten
+        busy[0].synchronize()
+    offsets = {k: int(layout["staging"][row] if row in jrows else geom[row, 0]) for row, k in enumerate(kept)}
+    return kept, h2d, types.SimpleNamespace(slot=slot, geom=geom, totals=totals, layout=layout, offsets=offsets,
+                                            staged={kept[row] for row in jrows})
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # images
 # ----------------------------------------------------------------------------------------------------------------------
-class ImageEmbedPipeline:
+class ImageEmbedPipeline(_EncodeJob):
     """The image job (meerqat/image/embedding.py:125-166) with the host stages of batch i + 1 -- file decoding, packing the
     decoded RGB images into one pinned buffer, H2D and the Pillow-exact resize / crop / normalise kernels on a side stream --
     hidden behind the CLIP forward of batch i.  Needs the device-side transform (``transform.on_device``)."""
 
     def __init__(self, dataset, model, transform, save_as, image_key, call, pool, batch_size, depth=2, decode_procs=None,
                  decode_pool=None):
-        self.model, self.transform, self.save_as, self.image_key, self.call, self.pool = model, transform, save_as, image_key, call, pool
+        self.transform, self.save_as, self.call, self.pool = transform, save_as, call, pool
         self.column = _arrow_strings(dataset, image_key)
-        n = len(dataset)
-        self.bounds = [(s, min(s + batch_size, n)) for s in range(0, n, batch_size)]
-        first = next(iter(model.parameters()), None)
-        self.device = (first if first is not None else next(iter(model.buffers()))).device
-        self.main = torch.cuda.current_stream(self.device)
-        self.side = torch.cuda.Stream(device=self.device)
-        self.out_ring = _PinnedRing(3)
-        self.stats = {"batches": 0, "decode_s": 0.0, "prepare_s": 0.0, "launch_s": 0.0, "wait_result_s": 0.0}
         # Decoding.  Default: forked decode PROCESSES that write the RGB bytes straight into a shared page-locked staging slot
         # (viquae_amd/image/decode_pool.py: Pillow's per-file Python holds the GIL, threads stop scaling at ~2x; `processes`
         # of the reference's config sets their number, MQ_IMAGE_DECODE_PROCS the default, 0 disables).  Otherwise the caller's
@@ -464,112 +542,68 @@ class ImageEmbedPipeline:
             from concurrent.futures import ThreadPoolExecutor
             self.threads = ThreadPoolExecutor(max(1, int(os.environ.get("MQ_IMAGE_DECODE_THREADS", min(8, os.cpu_count() or 1)))))
         self._slot_busy = {}
-        self.stats["decode"] = (f"{len(self.decode.procs)} processes -> shared pinned staging" if self.decode is not None else
-                                "caller's process pool" if pool is not None else f"{self.threads._max_workers} threads")
-        self.look = Lookahead(len(self.bounds), self._prepare, self._launch, depth=depth)
+        decode = (f"{len(self.decode.procs)} processes -> shared pinned staging" if self.decode is not None else
+                  "caller's process pool" if pool is not None else f"{self.threads._max_workers} threads")
+        super().__init__(dataset, model, image_key, batch_size, {"decode_s": 0.0, "decode": decode}, depth=depth)
+
+    def _prepared(self, names, kept, failed, inputs, ev):
+        return {"names": names, "event": ev, "tensors": list(inputs.values()) if inputs else [], "info": (kept, failed),
+                "inputs": inputs}
 
     def _prepare_shared(self, names, t0):
-        """Decode workers: sizes -> plan -> decode into the planned offsets of a shared slot -> device-side transform."""
+        """Decode workers: sizes -> plan -> decode into the planned offsets of a shared slot -> device-side transform.  None
+        when the batch does not fit a slot."""
         from .data import loading
-        paths = [str(loading.IMAGE_PATH / n) for n in names]
-        sizes = self.decode.sizes(paths)
-        kept = [i for i, sz in enumerate(sizes) if sz is not None]
+        kept, _, st = _stage_decode(self.decode, self._slot_busy, [str(loading.IMAGE_PATH / n) for n in names], self.transform.plan)
         if not kept:
-            return kept, set(), None, None
-        geom, totals = self.transform.plan(np.array([sizes[i] for i in kept], dtype=np.int64))
-        # JPEG files whose scans the workers decode (decode_pool.last_jpeg): staging areas instead of RGB bytes in the slot, their
-        # RGB produced on the device (viquae_amd/image/jpeg.py)
-        jrows = {row: self.decode.last_jpeg[k] for row, k in enumerate(kept) if k in self.decode.last_jpeg}
-        layout = None
-        if jrows:
-            from .image import jpeg as dj
-            layout = dj.plan_layout(geom, totals, jrows)
-        if layout is not None and int(layout["h2d_bytes"]) > self.decode.slot_bytes:
-            # coefficients take 2 bytes per sample: a batch of 4:4:4 files can outgrow a slot its RGB bytes fit -- the workers
-            # then decode this batch's files with Pillow, as they do for every other format
-            geom, totals = self.transform.plan(np.array([sizes[i] for i in kept], dtype=np.int64))
-            jrows, layout = {}, None
-        if int(layout["h2d_bytes"] if layout else totals[0]) > self.decode.slot_bytes:
+            return self._prepared(names, kept, set(), None, None)
+        if st is None:
             return None  # larger images than the slots were sized for: this batch takes the thread (or caller's pool) path
-        slot = self.decode.take_slot()
-        busy = self._slot_busy.pop(slot, None)
-        if busy is not None:      # the copy that last read this slot (two batches ago) must be over before it is rewritten
-            busy[0].synchronize()
-        failed = self.decode.decode(slot, {k: int(layout["staging"][row] if row in jrows else g[0]) for row, (k, g) in enumerate(zip(kept, geom))},
-                                    staged={k for row, k in enumerate(kept) if row in jrows})
-        self.stats["jpeg_scans_decoded_by_workers"] = self.stats.get("jpeg_scans_decoded_by_workers", 0) + len(jrows)
+        failed = self.decode.decode(st.slot, st.offsets, staged=st.staged)
+        self.stats["jpeg_scans_decoded_by_workers"] = self.stats.get("jpeg_scans_decoded_by_workers", 0) + len(st.staged)
         self.stats["decode_s"] += time.perf_counter() - t0
         with torch.cuda.device(self.device), torch.cuda.stream(self.side):
             # enqueued only: the DMA of this slot and the resize kernels run while the workers decode the NEXT batch into the
             # other slot
-            got = self.transform.run_packed(self.decode.tensors[slot], geom, totals, len(kept), sync=False, jpeg=layout)
+            got = self.transform.run_packed(self.decode.tensors[st.slot], st.geom, st.totals, len(kept), sync=False, jpeg=st.layout)
             ev = torch.cuda.Event()
             ev.record(self.side)
-        self._slot_busy[slot] = (ev, got.pop("_keep", None))
-        return kept, failed, dict(got), ev
+        self._slot_busy[st.slot] = (ev, got.pop("_keep", None))
+        return self._prepared(names, kept, failed, dict(got), ev)
 
     def _prepare(self, j):
         from .data.loading import load_image_array, load_image_batch
         t0 = time.perf_counter()
         s, e = self.bounds[j]
         names = self.column.slice(s, e - s).to_pylist()
-        if self.decode is not None:
-            got = self._prepare_shared(names, t0)
-            if got is not None:
-                kept, failed, inputs, ev = got
-                self.stats["prepare_s"] += time.perf_counter() - t0
-                return {"names": names, "kept": kept, "failed": failed, "inputs": inputs, "event": ev, "rows": len(names)}
-        if self.threads is not None:
-            images = list(self.threads.map(load_image_array, names))
-        else:
-            images = load_image_batch(names, pool=self.pool, as_arrays=True)
-        kept = [i for i, im in enumerate(images) if im is not None]
-        self.stats["decode_s"] += time.perf_counter() - t0
-        inputs = ev = None
-        if kept:
-            with torch.cuda.device(self.device), torch.cuda.stream(self.side):
-                inputs = dict(self.transform([images[i] for i in kept], return_tensors="pt"))  # packs, copies, runs its kernels HERE
-                ev = torch.cuda.Event()
-                ev.record(self.side)
+        p = self._prepare_shared(names, t0) if self.decode is not None else None
+        if p is None:
+            if self.threads is not None:
+                images = list(self.threads.map(load_image_array, names))
+            else:
+                images = load_image_batch(names, pool=self.pool, as_arrays=True)
+            kept = [i for i, im in enumerate(images) if im is not None]
+            self.stats["decode_s"] += time.perf_counter() - t0
+            inputs = ev = None
+            if kept:
+                with torch.cuda.device(self.device), torch.cuda.stream(self.side):
+                    inputs = dict(self.transform([images[i] for i in kept], return_tensors="pt"))  # packs, copies, runs its kernels HERE
+                    ev = torch.cuda.Event()
+                    ev.record(self.side)
+            p = self._prepared(names, kept, set(), inputs, ev)
         self.stats["prepare_s"] += time.perf_counter() - t0
-        return {"names": names, "kept": kept, "failed": set(), "inputs": inputs, "event": ev, "rows": len(names)}
+        return p
 
-    def _launch(self, p):
-        t0 = time.perf_counter()
-        if not p["kept"]:
-            return _Handle(None, torch.empty((0, 1)), 0, extra=(p["names"], p["kept"], p["failed"], p["rows"]))
-        with torch.cuda.device(self.device):
-            self.main.wait_event(p["event"])
-            for t in p["inputs"].values():
-                t.record_stream(self.main)
-            method = self.model if self.call is None else getattr(self.model, self.call)
-            with torch.no_grad():
-                out = method(**p["inputs"])
-            if not isinstance(out, torch.Tensor):  # transformers >= 5 returns a ModelOutput
-                out = out.pooler_output
-            out = out.reshape(len(p["kept"]), -1).to(torch.float32).contiguous()
-            slot, buf = self.out_ring.take(out.numel() * 4)
-            pinned = buf[: out.numel() * 4].view(torch.float32).view(out.shape)
-            pinned.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.out_ring.events[slot] = ev
-        self.stats["launch_s"] += time.perf_counter() - t0
-        return _Handle(ev, pinned, len(p["kept"]), extra=(p["names"], p["kept"], p["failed"], p["rows"]))
+    def _forward(self, p):
+        method = self.model if self.call is None else getattr(self.model, self.call)
+        out = method(**p["inputs"])
+        if not isinstance(out, torch.Tensor):  # transformers >= 5 returns a ModelOutput
+            out = out.pooler_output
+        return out.reshape(len(p["info"][0]), -1)
 
-    def embed(self, batch, indices):
-        i = self.stats["batches"]
-        s, e = self.bounds[i] if i < len(self.bounds) else (-1, -1)
-        if len(indices) != e - s or int(indices[0]) != s or int(indices[-1]) != e - 1:
-            raise RuntimeError("Dataset.map handed over batches in another order than the prefetcher prepared them; "
-                               "set MQ_EMBED_PIPELINE=0")
-        t0 = time.perf_counter()
-        found, (names, kept, failed, rows) = self.look.step(i)
-        self.stats["wait_result_s"] += time.perf_counter() - t0
-        if names != batch[self.image_key]:
-            raise RuntimeError(f"the prefetched file names of batch {i} differ from what Dataset.map decoded; set MQ_EMBED_PIPELINE=0")
-        self.stats["batches"] = i + 1
-        self.stats.setdefault("returned_at", []).append(time.perf_counter())
+    def _result(self, batch, found, info):
+        kept, failed = info
+        rows = len(batch[self.key])
         if len(kept) == rows and not failed:
             batch[self.save_as] = found   # every image was readable: ONE [B, H] array (Arrow ingests it without a per-row pass)
             return batch
@@ -583,8 +617,7 @@ class ImageEmbedPipeline:
         return batch
 
     def close(self):
-        self.stats["wait_prepared_s"] = self.look.wait_prepared_s
-        self.look.close()
+        super().close()
         if self.threads is not None:
             self.threads.shutdown(wait=False)
         if self.decode is not None:
@@ -593,20 +626,18 @@ class ImageEmbedPipeline:
 
 def image_pipeline_or_none(dataset, map_kwargs, model=None, transform=None, save_as="image_embedding", image_key="image", call=None,
                            pool=None, decode_procs=None, decode_pool=None, **other):
-    if not pipeline_enabled() or other or model is None or transform is None or not getattr(transform, "on_device", False):
+    """An :class:`ImageEmbedPipeline` when the transform runs on the device, else None; ``decode_pool`` becomes the pipeline's."""
+    bs = _job_batch_size(dataset, map_kwargs, model, image_key, not other and getattr(transform, "on_device", False), decode_pool)
+    if bs is None:
         return None
-    if not torch.cuda.is_available() or not _plain_dataset(dataset, map_kwargs) or _arrow_strings(dataset, image_key) is None:
-        return None
-    if _map_batch_size(map_kwargs) is None:
-        return None
-    return ImageEmbedPipeline(dataset, model, transform, save_as, image_key, call, pool, _map_batch_size(map_kwargs),
-                              decode_procs=decode_procs, decode_pool=decode_pool)
+    return ImageEmbedPipeline(dataset, model, transform, save_as, image_key, call, pool, bs, decode_procs=decode_procs,
+                              decode_pool=decode_pool)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # faces
 # ----------------------------------------------------------------------------------------------------------------------
-class FaceEmbedPipeline:
+class FaceEmbedPipeline(_EncodeJob):
     """The face job (meerqat/image/face_recognition.py:72-112: per batch, load every image that has ``face_landmarks``, align its
     first ``max_n_faces`` faces, run ArcFace) with the host stages of batch i + 1 -- file decoding by the decode workers (JPEG
     files: Huffman scan only, viquae_amd/image/jpeg.py), the 2 x 3 alignment matrices, H2D, the rest of the JPEG decoding and the
@@ -615,21 +646,14 @@ class FaceEmbedPipeline:
 
     def __init__(self, dataset, model, max_n_faces, image_key, batch_size, decode_pool, depth=2):
         from .image import face_recognition as fr
-        self.fr, self.model, self.max_n_faces, self.image_key, self.decode = fr, model, int(max_n_faces), image_key, decode_pool
+        self.fr, self.max_n_faces, self.decode = fr, int(max_n_faces), decode_pool
         self.names = _arrow_strings(dataset, image_key)
         self.landmarks = dataset.data.column("face_landmarks")
-        n = len(dataset)
-        self.bounds = [(s, min(s + batch_size, n)) for s in range(0, n, batch_size)]
-        first = next(iter(model.parameters()), None)
-        self.device = (first if first is not None else next(iter(model.buffers()))).device
-        self.main = torch.cuda.current_stream(self.device)
-        self.side = torch.cuda.Stream(device=self.device)
-        self.out_ring = _PinnedRing(3)
         self._slot_busy = {}
         self.tform = fr.SimilarityTransform()
-        self.stats = {"batches": 0, "decode_s": 0.0, "prepare_s": 0.0, "launch_s": 0.0, "wait_result_s": 0.0, "faces": 0,
-                      "decode": f"{len(decode_pool.procs)} processes -> shared pinned staging"}
-        self.look = Lookahead(len(self.bounds), self._prepare, self._launch, depth=depth)
+        super().__init__(dataset, model, image_key, batch_size,
+                         {"decode_s": 0.0, "faces": 0, "decode": f"{len(decode_pool.procs)} processes -> shared pinned staging"},
+                         depth=depth)
 
     def _prepare(self, j):
         from .data import loading
@@ -640,39 +664,18 @@ class FaceEmbedPipeline:
         names = self.names.slice(s, e - s).to_pylist()
         marks = self.landmarks.slice(s, e - s).to_pylist()
         wanted = [i for i, lm in enumerate(marks) if lm is not None]      # only images with detected faces are loaded (:81-83)
-        empty = {"names": names, "rows": len(names), "images": [], "counts": [], "inputs": None, "event": None}
+        empty = {"names": names, "event": None, "info": ([], [])}
         if not wanted:
             return empty
-        sizes = self.decode.sizes([str(loading.IMAGE_PATH / names[i]) for i in wanted])
-        kept = [k for k, sz in enumerate(sizes) if sz is not None]         # positions in `wanted` of the readable files
+        kept, h2d, st = _stage_decode(self.decode, self._slot_busy, [str(loading.IMAGE_PATH / names[i]) for i in wanted], _rgb_plan)
         if not kept:
             return empty
-        geom = np.zeros((len(kept), 3), dtype=np.int64)                    # (offset, height, width) like mq_image_plan's first columns
-        geom[:, 1:] = [sizes[k] for k in kept]
-        totals = np.zeros(1, dtype=np.int64)
-        jrows = {row: self.decode.last_jpeg[k] for row, k in enumerate(kept) if k in self.decode.last_jpeg}
-        layout = None
-        if jrows:
-            layout = dj.plan_layout(geom, totals, jrows)
-        if not jrows or int(layout["h2d_bytes"]) > self.decode.slot_bytes:   # (coefficients can outgrow a slot the RGB bytes fit)
-            off = 0
-            for row in range(len(kept)):
-                geom[row, 0] = off
-                off += (int(geom[row, 1]) * int(geom[row, 2]) * 3 + 15) & ~15
-            totals[0] = off
-            jrows, layout = {}, None
-        h2d = int(layout["h2d_bytes"] if layout else totals[0])
-        if h2d > self.decode.slot_bytes:
+        if st is None:
             raise RuntimeError(f"a batch of {len(kept)} images needs {h2d} bytes of staging, the slots hold {self.decode.slot_bytes}: "
                                "raise MQ_IMAGE_SLOT_KB or set MQ_EMBED_PIPELINE=0")
-        slot = self.decode.take_slot()
-        busy = self._slot_busy.pop(slot, None)
-        if busy is not None:      # the copy that last read this slot (two batches ago) must be over before it is rewritten
-            busy[0].synchronize()
         # the faces' alignment matrices (Umeyama's estimate per face: ~50 us of small numpy calls each) are the workers' job too
         self.decode.call_start("viquae_amd.image.face_recognition", "face_matrices", {k: (marks[wanted[k]], self.max_n_faces) for k in kept})
-        self.decode.decode_start(slot, {k: int(layout["staging"][row] if row in jrows else geom[row, 0]) for row, k in enumerate(kept)},
-                                 staged={k for row, k in enumerate(kept) if row in jrows})
+        self.decode.decode_start(st.slot, st.offsets, staged=st.staged)
         mats = self.decode.call_finish()
         per_image = [mats[k] for k in kept]
         failed = self.decode.decode_finish()
@@ -687,14 +690,15 @@ class FaceEmbedPipeline:
             for m in per_image[row][1]:
                 owner.append(row)
                 minv.append(m)
-        out = dict(empty, images=images, counts=counts)
+        out = dict(empty, info=(images, counts))
         if not owner:
             return out
         lib = _lib.load()
+        geom, layout = st.geom, st.layout
         with torch.cuda.device(self.device), torch.cuda.stream(self.side):
             dev = self.device
-            src = torch.empty(int(totals[0]), dtype=torch.uint8, device=dev)
-            src[:h2d].copy_(self.decode.tensors[slot][:h2d], non_blocking=True)
+            src = torch.empty(int(st.totals[0]), dtype=torch.uint8, device=dev)
+            src[:h2d].copy_(self.decode.tensors[st.slot][:h2d], non_blocking=True)
             keep = [src]
             if layout is not None:
                 keep.append(dj.decode_staged(src, layout["items"], layout["max_blocks"], layout["max_strips"]))
@@ -708,44 +712,18 @@ class FaceEmbedPipeline:
             ev = torch.cuda.Event()
             ev.record(self.side)
             keep += [off_d, hw_d, own_d, minv_d]
-        self._slot_busy[slot] = (ev, keep)
+        self._slot_busy[st.slot] = (ev, keep)
         self.stats["prepare_s"] += time.perf_counter() - t0
         self.stats["faces"] += len(owner)
-        out.update(inputs=px, event=ev)
+        out.update(event=ev, tensors=[px], inputs=px)
         return out
 
-    def _launch(self, p):
-        t0 = time.perf_counter()
-        extra = (p["names"], p["images"], p["counts"], p["rows"])
-        if p["inputs"] is None:
-            return _Handle(None, torch.empty((0, 1)), 0, extra=extra)
-        with torch.cuda.device(self.device):
-            self.main.wait_event(p["event"])
-            p["inputs"].record_stream(self.main)
-            with torch.no_grad():
-                out = self.model(p["inputs"]).to(torch.float32).contiguous()
-            slot, buf = self.out_ring.take(out.numel() * 4)
-            pinned = buf[: out.numel() * 4].view(torch.float32).view(out.shape)
-            pinned.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            self.out_ring.events[slot] = ev
-        self.stats["launch_s"] += time.perf_counter() - t0
-        return _Handle(ev, pinned, out.shape[0], extra=extra)
+    def _forward(self, p):
+        return self.model(p["inputs"])
 
-    def embed(self, batch, indices):
-        i = self.stats["batches"]
-        s, e = self.bounds[i] if i < len(self.bounds) else (-1, -1)
-        if len(indices) != e - s or int(indices[0]) != s or int(indices[-1]) != e - 1:
-            raise RuntimeError("Dataset.map handed over batches in another order than the prefetcher prepared them; set MQ_EMBED_PIPELINE=0")
-        t0 = time.perf_counter()
-        found, (names, images, counts, rows) = self.look.step(i)
-        self.stats["wait_result_s"] += time.perf_counter() - t0
-        if names != batch[self.image_key]:
-            raise RuntimeError(f"the prefetched file names of batch {i} differ from what Dataset.map decoded; set MQ_EMBED_PIPELINE=0")
-        self.stats["batches"] = i + 1
-        self.stats.setdefault("returned_at", []).append(time.perf_counter())
-        output = [None] * rows
+    def _result(self, batch, found, info):
+        images, counts = info
+        output = [None] * len(batch[self.key])
         j = 0
         if sum(counts):   # (a batch without a single face: every entry None, like the reference's early return)
             for at, n_faces in zip(images, counts):
@@ -755,22 +733,45 @@ class FaceEmbedPipeline:
         return batch
 
     def close(self):
-        self.stats["wait_prepared_s"] = self.look.wait_prepared_s
-        self.look.close()
+        super().close()
         self.decode.close()
 
 
 def face_pipeline_or_none(dataset, map_kwargs, model=None, max_n_faces=1, image_key="image", decode_pool=None, **other):
-    """The pipelined face job, or None when it does not apply (then ``compute_face_embedding`` is mapped as the reference does)."""
-    if not pipeline_enabled() or other or model is None or decode_pool is None or not torch.cuda.is_available():
+    """The pipelined face job, or None when it does not apply (then ``compute_face_embedding`` is mapped as the reference does);
+    ``decode_pool`` becomes the pipeline's."""
+    bs = _job_batch_size(dataset, map_kwargs, model, image_key,
+                         not other and decode_pool is not None and "face_landmarks" in dataset.column_names, decode_pool)
+    if bs is None:
         return None
-    if not _plain_dataset(dataset, map_kwargs) or _arrow_strings(dataset, image_key) is None or "face_landmarks" not in dataset.column_names:
+    return FaceEmbedPipeline(dataset, model, max_n_faces, image_key, bs, decode_pool)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the job driver of image.embedding.dataset_embed, ir.embedding.dataset_embed and face_recognition.dataset_compute_face_embedding
+# ----------------------------------------------------------------------------------------------------------------------
+def early_decode_pool(processes, map_kwargs):
+    """The decode workers of an image / face job mapped with ``map_kwargs`` (image.decode_pool.early_pool: to be forked before
+    the caller loads its model), or None when the pipeline does not apply."""
+    bs = _map_batch_size(map_kwargs)
+    if bs is None:
         return None
-    if _map_batch_size(map_kwargs) is None:
-        return None
-    first = next(iter(model.parameters()), None) if hasattr(model, "parameters") else None
-    if first is None and hasattr(model, "buffers"):
-        first = next(iter(model.buffers()), None)
-    if first is None or not first.is_cuda:
-        return None
-    return FaceEmbedPipeline(dataset, model, max_n_faces, image_key, _map_batch_size(map_kwargs), decode_pool)
+    from .image.decode_pool import early_pool
+    return early_pool(processes, bs)
+
+
+def map_encode_job(job, dataset, map_kwargs, pipe, serial, fn_kwargs, fingerprint=None):
+    """``Dataset.map`` of ``pipe.embed``, or of ``serial`` with ``fn_kwargs`` when there is no pipeline; sets
+    ``job.last_pipeline_stats``.  The pipelined map is named ``fingerprint()`` unless ``map_kwargs`` names it: ``datasets`` would
+    hash the pipeline's bound method by pickling the model's weights and the whole input column."""
+    map_kwargs = dict(map_kwargs)
+    if pipe is None:
+        job.last_pipeline_stats = None
+        return dataset.map(serial, batched=True, fn_kwargs=fn_kwargs, **map_kwargs)
+    if "new_fingerprint" not in map_kwargs:
+        map_kwargs["new_fingerprint"] = fingerprint()
+    try:
+        return dataset.map(pipe.embed, batched=True, with_indices=True, **map_kwargs)
+    finally:
+        pipe.close()
+        job.last_pipeline_stats = dict(pipe.stats)
