@@ -272,3 +272,45 @@ def test_blas_leg_equals_the_chain_oracle_on_lattice_data(metric):
     Db, Ib = ok.knn_blas(X[:40], Q, 64, metric=metric)  # k > ntotal: neutral values and -1
     D, I = ok.knn(X[:40], Q, 64, metric=metric, l2_form="expanded")
     assert np.array_equal(D, Db) and np.array_equal(I, Ib)
+
+
+def _scale_data(nq):
+    from tests.knn_scale_data import planted
+    return planted(11 + nq, 3000, 40, nq, 60, bases=5)
+
+
+@pytest.mark.parametrize("nq", [7, 25])
+def test_oracle_inner_product_is_invariant_under_opposite_power_of_two_scales(nq):
+    """(X 2^s, Q 2^-s): the same products q_i x_i, so the same fp32 chains -- D and I bit-identical over the whole sweep of
+    tests/test_knn_scale_gpu.py (the premise of that file: a GPU mismatch there is the GPU path's)."""
+    from tests.knn_scale_data import IP_SWEEP, scaled
+    X, Q = _scale_data(nq)
+    D0, I0 = ok.knn(X, Q, 50, metric=0)
+    for s in IP_SWEEP:
+        for a, b in ((s, -s), (-s, s)):
+            D, I = ok.knn(scaled(X, a), scaled(Q, b), 50, metric=0)
+            assert np.array_equal(I, I0) and np.array_equal(D, D0), (a, b)
+
+
+@pytest.mark.parametrize("nq", [7, 25])  # FAISS's direct form below 20 queries, the clamped expansion from 20 on
+def test_oracle_l2_scales_by_four_to_the_s(nq):
+    from tests.knn_scale_data import L2_SWEEP, scaled
+    X, Q = _scale_data(nq)
+    D0, I0 = ok.knn(X, Q, 50, metric=1)
+    assert (D0 > 0).all() and np.isfinite(D0).all()
+    for s in L2_SWEEP:
+        D, I = ok.knn(scaled(X, s), scaled(Q, s), 50, metric=1)
+        assert np.array_equal(I, I0) and np.array_equal(D, scaled(D0, 2 * s)), s
+
+
+@pytest.mark.parametrize("form", ["numpy", "faiss"])
+@pytest.mark.parametrize("metric", [0, 1])
+def test_oracle_l2norm_rows_are_invariant_under_power_of_two_scales(form, metric):
+    """"L2norm,": x 2^s / ||x 2^s|| is x / ||x|| bit for bit in both arithmetics while ||x||^2 stays a normal number."""
+    from tests.knn_scale_data import L2NORM_SWEEP, scaled
+    X, Q = _scale_data(25)
+    assert np.array_equal(ok.l2norm_rows(scaled(X, 55), form), ok.l2norm_rows(X, form))
+    D0, I0 = ok.knn(X, Q, 50, metric=metric, l2norm=True, l2norm_form=form)
+    for s in L2NORM_SWEEP:
+        D, I = ok.knn(scaled(X, s), scaled(Q, -s if metric == 0 else s), 50, metric=metric, l2norm=True, l2norm_form=form)
+        assert np.array_equal(I, I0) and np.array_equal(D, D0), s

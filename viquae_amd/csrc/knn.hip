@@ -1569,7 +1569,8 @@ static int screen_copy_and_stats(const float* sqnorm_dev, int d, int metric, int
                            (unsigned short*)bf16_dev, metric == MQ_METRIC_L2 ? 1 : 0, sqnorm_dev + row_offset, center_dev, row_offset);
     MQ_HIP(hipGetLastError());
     hipLaunchKernelGGL(row_err_stats_kernel, dim3((unsigned)((n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048)), dim3(256), 0, st, rm,
-                       (const unsigned short*)bf16_dev, n, d, dp, (unsigned*)xstats_dev, center_dev, row_offset);
+                       (const unsigned short*)bf16_dev, n, d, dp, (unsigned*)xstats_dev, center_dev, row_offset,
+                       metric == MQ_METRIC_L2 ? 1 : 0);
     MQ_HIP(hipGetLastError());
     return MQ_OK;
 }
@@ -1842,7 +1843,7 @@ int mq_knn_screen_stats(int64_t N, int d, int nq, int k, const void* ws_dev, int
     }
     float mm = 0.f;
     for (int i = 0; i < nq; ++i) if (mg[i] > mm || mg[i] != mg[i]) mm = mg[i];
-    out[5] = (int64_t)(mm * 1e6f);  /* max margin in 1e-6 units */
+    out[5] = mm < 9e12f ? (int64_t)(mm * 1e6f) : INT64_MAX;  /* max margin in 1e-6 units (INT64_MAX: infinite) */
     out[6] = g.S;
     free(ovf); free(cc); free(pc); free(mg);
     if (e1 != hipSuccess) return hip_fail(e1);

@@ -174,33 +174,43 @@ __global__ __launch_bounds__(256) void to_bf16_rows_centred_kernel(const float* 
 // Shard statistics of the error bound, updated by every mq_knn_screen_prepare call (atomic max on the bit patterns
 // of non-negative floats): stats[0] = max ||x||^2, stats[1] = max ||x - bf16(x)||^2.  x - bf16(x) is exact in fp32;
 // the fp32 sums carry a relative error <= (dp + 1) 2^-24, covered by the slack factors of screen_margin_kernel.
-// Rows with a non-finite norm are skipped (their scores are non-finite on every path anyway).
+// A row with an inf / NaN element is skipped: its scores are non-finite on every path, or never enter a result.  A row of finite
+// elements whose sums overflow is NOT harmless: with the inner product its scores stay finite against small queries (x ~ 2^64,
+// q ~ 2^-64), so it records +inf in every statistic -- the margin turns infinite and the tiles fall back to the exact scan.  L2
+// (l2 = 1) skips such a row when ||x||^2 itself overflows: its distance is then infinite on every path.  Sums that UNDERflow
+// are covered in screen_margin_kernel (an absolute floor of d 2^-148 under every squared sum).
 // stats[2] = max ||x - c||^2 (= stats[0] without a centre); stats[1] is then max ||(x - c) - bf16(x - c)||^2;
 // stats[3] = max |c . (x - c)| (0 without a centre): the row term of the centred-query screen.
 // xb = the whole bf16 copy (tile layout), rm = the row-major rows from row `row0` on.
 __global__ __launch_bounds__(256) void row_err_stats_kernel(const float* __restrict__ rm, const unsigned short* __restrict__ xb,
                                                             int64_t n, int d, int dp, unsigned* __restrict__ stats,
-                                                            const float* __restrict__ center, int64_t row0) {
+                                                            const float* __restrict__ center, int64_t row0, int l2) {
     const int lane = threadIdx.x & 63;
     float ms2 = 0.f, me2 = 0.f, mc2 = 0.f, mv = 0.f;  // this wave's running maxima: one set of atomics per wave, not per row
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {
         float s2 = 0.f, e2 = 0.f, c2 = 0.f, v = 0.f;
+        int nf = 0;  // inf / NaN elements of the row
         for (int k = lane; k < d; k += 64) {
             const float x = rm[r * d + k];
             const float xc = center ? x - center[k] : x;
             const float e = xc - s16_to_f32(xb[xb_tile_index(row0 + r, k, dp)]);
+            nf += !(fabsf(x) < INFINITY);
             s2 += x * x;
             e2 += e * e;
             c2 += xc * xc;
             if (center) v += center[k] * xc;
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { s2 += __shfl_xor(s2, o); e2 += __shfl_xor(e2, o); c2 += __shfl_xor(c2, o); v += __shfl_xor(v, o); }
+        for (int o = 32; o > 0; o >>= 1) {
+            s2 += __shfl_xor(s2, o); e2 += __shfl_xor(e2, o); c2 += __shfl_xor(c2, o); v += __shfl_xor(v, o); nf += __shfl_xor(nf, o);
+        }
         if (s2 < INFINITY && e2 < INFINITY && c2 < INFINITY) {  // false for NaN as well
             ms2 = fmaxf(ms2, s2);
             me2 = fmaxf(me2, e2);
             mc2 = fmaxf(mc2, c2);
-            if (fabsf(v) < INFINITY) mv = fmaxf(mv, fabsf(v));
+            mv = fmaxf(mv, fabsf(v) < INFINITY ? fabsf(v) : (nf == 0 ? INFINITY : 0.f));
+        } else if (nf == 0 && !(l2 && !(s2 < INFINITY))) {  // finite elements, overflowing sums: see above
+            ms2 = me2 = mc2 = mv = INFINITY;
         }
     }
     if (lane == 0) {
@@ -274,21 +284,30 @@ __global__ __launch_bounds__(256) void screen_margin_kernel(const float* __restr
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { q2 += __shfl_xor(q2, o); dq2 += __shfl_xor(dq2, o); qu2 += __shfl_xor(qu2, o); c2 += __shfl_xor(c2, o); }
-    const float qn = sqrtf(q2) * 1.001f, dqn = sqrtf(dq2) * 1.001f;
+    // Underflow: a square or a sum below 2^-126 is rounded with an ABSOLUTE error of at most 2^-150, so each of these sums of d
+    // squares (and the chain of c . xc) can fall short by at most d 2^-150 -- even to 0 for a non-zero row (x ~ 2^-66: the
+    // rounding errors squared vanish while the scores, against queries ~ 2^66, stay ordinary numbers).  uf = d 2^-148 added
+    // under every sum keeps each factor an upper bound; at ordinary scales it is far below the sums' last bit.
+    const float uf = (float)d * 0x1p-148f;
+    const float qn = sqrtf(q2 + uf) * 1.001f, dqn = sqrtf(dq2 + uf) * 1.001f;
     // xstats: max ||x||^2, max ||xc - xc~||^2, max ||xc||^2 with xc = x - c the rows the screen actually rounds (c = 0
     // unless the index centred its bf16 copy).  The two rounding terms live on the centred rows; the accumulation
     // slack covers the bf16 MFMA on (q~, xc~) AND the fp32 chain of the exact scores on (q, x): it takes the larger norm.
-    const float xun = sqrtf(xstats[0]) * 1.001f, dxn = sqrtf(xstats[1]) * 1.001f, xcn = sqrtf(xstats[2]) * 1.001f;
+    const float xun = sqrtf(xstats[0] + uf) * 1.001f, dxn = sqrtf(xstats[1] + uf) * 1.001f, xcn = sqrtf(xstats[2] + uf) * 1.001f;
     const float xn = fmaxf(xun, xcn);
+    // A factor that overflowed (+inf) times one that underflowed (0) would make the margin NaN, and a NaN margin reads as a
+    // padding query (margin >= 0 false) to every kernel behind this one: any margin that is not a number >= 0 becomes +inf,
+    // which keeps every row and sends the tile to the exact scan.
     if (mode == 2) {
-        const float qun = sqrtf(qu2) * 1.001f, cn = sqrtf(c2) * 1.001f, vmax = xstats[3] * 1.001f;
+        const float qun = sqrtf(qu2 + uf) * 1.001f, cn = sqrtf(c2 + uf) * 1.001f, vmax = (xstats[3] + uf) * 1.001f;
         const float u = 5.9604645e-8f;  // 2^-24
         float eps = qn * dxn + dqn * xcn * 1.002f;
         eps += (float)dp * 2.3842e-7f * 1.004f * (qn * xcn + vmax);
         eps += (float)d * u * 1.004f * qun * xun;
         eps += 7.63e-6f * vmax + (float)d * u * 1.004f * (vmax + cn * xcn);
         eps += 2.0f * u * (qun + qn) * xcn;
-        if (lane == 0) margin[q] = (2.0f * eps) * 1.001f + 1e-30f;
+        const float m = (2.0f * eps) * 1.001f + 1e-30f;
+        if (lane == 0) margin[q] = m >= 0.f ? m : INFINITY;
         return;
     }
     // dp * (2^-22 for the bf16 MFMA's fp32 accumulation, taken 4x the textbook bound because its internal summation
@@ -301,7 +320,8 @@ __global__ __launch_bounds__(256) void screen_margin_kernel(const float* __restr
         eps += ((float)dp * 1.2e-7f + 7.63e-6f) * x2 + 1.51f * u * (q2u + x2);
         extra = (1.01f * (float)d + 1.51f) * u * (q2u + x2);
     }
-    if (lane == 0) margin[q] = (2.0f * eps + extra) * 1.001f + 1e-30f;
+    const float m = (2.0f * eps + extra) * 1.001f + 1e-30f;
+    if (lane == 0) margin[q] = m >= 0.f ? m : INFINITY;
 }
 
 struct ScreenArgs {
@@ -952,6 +972,10 @@ __global__ __launch_bounds__(256) void cand_select_kernel(const u64* __restrict_
         // goes to the exact scan.
         const int filled = layout_word ? *layout_word : POOL_LAYOUT_SLICES;
         if (filled != LAYOUT) ovf[qt] = 1;
+        // an infinite margin (screen_margin_kernel: a factor of the bound overflowed) bounds nothing, and the bf16 scores of such
+        // data may be inf / NaN themselves (the centred screen's row term c . (x - c) at x ~ 2^100) and never reach a pool:
+        // the tile goes to the exact scan whatever the pools hold
+        if (!(margin[q] < INFINITY)) ovf[qt] = 1;
         state = (filled != LAYOUT || ovf[qt]) ? -1 : 0;
     }
     __syncthreads();

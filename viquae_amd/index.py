@@ -326,11 +326,13 @@ class MI355XFlatIndex(BaseIndex):
         self._screen_metric = self.metric_type
         # (a first add of a handful of rows says nothing about a common component: their mean IS most of them)
         if center is not None and self.metric_type == METRIC_INNER_PRODUCT and dev.shape[0] >= 256:
-            x = dev.to(torch.float32)
+            # float64: the fp32 squares overflow for rows ~ 2^64 (and vanish for rows ~ 2^-64) while the share does not depend
+            # on the scale of the data
+            x = dev.to(torch.float64)
             if self.do_l2norm:
                 x = torch.nn.functional.normalize(x, dim=1)
             x2 = float(torch.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0).pow(2).sum(1).mean())
-            share = float(center.pow(2).sum()) / x2 if x2 > 0 else 0.0
+            share = float(center.double().pow(2).sum()) / x2 if x2 > 0 else 0.0
             dp_plain, dp_cols = (int(d) + 63) // 64, (int(d) + 2 + 63) // 64
             free = dp_cols == dp_plain
             # free columns or a width the tile kernel serves anyway: a quarter of the squared norms; otherwise (a K block more:
