@@ -209,7 +209,7 @@ int mq_knn_screen_stats(int64_t N, int d, int nq, int k, const void *ws_dev, int
 /* Which screening scan mq_knn_search_screened_f32 runs for this problem on this device: the 256 x 256 tile kernel
  * (screen_scan_kernel) or, for ONE query tile (nq <= 256 -- the reference's Dataset.map batch,
  * experiments/ir/viquae/dpr/search/config.json:25 -> meerqat/ir/search.py:146) over a shard of at least 65,536 rows with at
- * most 768 bf16 columns and k <= 128, the streaming kernel that keeps the queries in registers (csrc/knn_small.inc).
+ * most 768 bf16 columns and k <= 128, the streaming kernel that keeps the queries in registers (csrc/knn_small8.inc).
  * For 225 <= k <= 1792 the answer describes the scan of one row range.
  * MQ_SCAN_KIND_NONE: the call is not served by a screening scan at all (k > 1792 or row ranges too small: exact rounds; fewer
  * than 20 L2 queries: FAISS's direct form).  Negative: MQ_EINVAL.  MQ_KNN_OPT_SMALL_SCAN = 0 (below) switches the streaming kernel
@@ -224,8 +224,8 @@ int mq_knn_screen_scan_kind(int64_t N, int d, int nq, int k, int metric);
  *   MQ_KNN_OPT_SMALL_SCAN        1 (default): one query tile may be served by the streaming kernel; 0: always the tile kernel
  *   MQ_KNN_OPT_SMALL_MIN_TILES   the streaming kernel's floor of 32-row tiles per workgroup; 0 (default) = the built-in 8
  *   MQ_KNN_OPT_PARTITIONS        1 (default): 225 <= k <= 1792 is served over row ranges; 0: exact rounds
- *   MQ_KNN_OPT_SMALL_WAVES       8 (default): the streaming kernel with two waves per SIMD (csrc/knn_small8.inc, round 5);
- *                                4: round 4's one wave per SIMD (csrc/knn_small.inc).  Environment: MQ_KNN_SMALL_WAVES
+ *   MQ_KNN_OPT_SMALL_WAVES       retired (it chose round 4's one-wave-per-SIMD streaming kernel, since removed): still accepted
+ *                                and stored, 8 at start, read by nothing -- kept so that old callers do not break
  * mq_knn_set_option returns the previous value, mq_knn_get_option the current one; MQ_EINVAL for an unknown key / negative value. */
 #define MQ_KNN_OPT_SMALL_SCAN 0
 #define MQ_KNN_OPT_SMALL_MIN_TILES 1

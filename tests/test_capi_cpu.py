@@ -71,8 +71,8 @@ def test_search_path_switches_are_set_through_the_abi(hip_lib):
 def test_streaming_kernels_do_not_spill():
     """The streaming scans keep queries in registers and an LDS-DMA ring in flight: a spilled register is a scratch reload inside
     the loop, whose `s_waitcnt vmcnt(0)` drains the ring every item.  The 12-K-block instances sit at the
-    register limit (two waves per SIMD: 128 + 128; one wave per SIMD: 256 + 256), so the invariant is checked at build time: hipcc's
-    kernel-resource remarks must report no scratch for every instance of both kernels and for the 256 x 256 tile kernel."""
+    register limit (two waves per SIMD: 128 + 128), so the invariant is checked at build time: hipcc's kernel-resource remarks must
+    report no scratch for every instance of the streaming kernel and for the 256 x 256 tile kernel."""
     import subprocess
     src = os.path.join(ROOT, "viquae_amd", "csrc", "knn.hip")
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off",
@@ -87,6 +87,10 @@ def test_streaming_kernels_do_not_spill():
         m = re.search(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and cur:
             seen[cur] = int(m.group(1))
-    watched = {k: v for k, v in seen.items() if "screen_small8_kernel" in k or "screen_small_kernel" in k or "screen_scan_kernel" in k}
-    assert len(watched) >= 25, sorted(watched)          # 12 + 12 streaming instances + the tile kernel
+    # every streaming instance ("screen_small" matches no kernel but screen_small8_kernel: round 4's one-wave kernel is retired)
+    watched = {k: v for k, v in seen.items() if "screen_small" in k or "screen_scan_kernel" in k}
+    expected = {"_ZN12_GLOBAL__N_118screen_scan_kernelENS_10ScreenArgsE"}
+    expected |= {f"_ZN12_GLOBAL__N_120screen_small8_kernelILi{nkb}ELb0EEEvNS_9SmallArgsE" for nkb in range(1, 13)}
+    expected.add("_ZN12_GLOBAL__N_120screen_small8_kernelILi12ELb1EEEvNS_9SmallArgsE")  # the ROWTERM instance
+    assert set(watched) == expected and len(expected) == 14, sorted(watched)
     assert all(v == 0 for v in watched.values()), {k: v for k, v in watched.items() if v}

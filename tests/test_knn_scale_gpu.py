@@ -25,7 +25,6 @@ def _default_switches():
     yield
     lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_SCAN, 1)
     lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_MIN_TILES, 0)
-    lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_WAVES, 8)
 
 
 def _index(X, metric, screen=True, factory="Flat", tie_order=None, l2norm_form=None, shards=0):
@@ -77,7 +76,7 @@ _IP_ROUTES = {
     "tile_uncentred": (30000, 128, 300, 50, 80, 8, {}, {"MQ_KNN_CENTER": "0"}, {}, "tile", True),
     "stream": (66000, 768, 40, 100, 150, 4, {}, {}, {}, "stream", True),
     "stream_centred_d768": (66000, 768, 40, 100, 150, 4, {}, {"MQ_KNN_CENTER_QUERIES": "1"}, {}, "stream", True),
-    "stream_one_wave": (66000, 256, 40, 64, 100, 4, {}, {}, {"SMALL_WAVES": 4}, "stream", True),
+    "stream_d256_k64": (66000, 256, 40, 64, 100, 4, {}, {}, {}, "stream", True),
     "exact": (20000, 64, 300, 50, 80, 8, {"screen": False}, {}, {}, "none", False),
     "wide_d1024": (8000, 1024, 280, 20, 40, 8, {}, {}, {}, "tile", True),
     "wide_d2048": (5000, 2048, 270, 20, 40, 8, {}, {}, {}, "tile", True),

@@ -1,4 +1,4 @@
-"""GPU: the streaming screening scan for ONE query tile (csrc/knn_small.inc: queries in registers, the whole LDS a ring of 32-row
+"""GPU: the streaming screening scan for ONE query tile (csrc/knn_small8.inc: queries in registers, the whole LDS a ring of 32-row
 tiles, one workgroup per CU) must give exactly what the 256 x 256 tile kernel, the exact fp32 scan and the CPU oracle give --
 scores bit for bit, ids, tie order.  It serves searches of at most 256 queries (the reference's ``Dataset.map`` batch,
 experiments/ir/viquae/dpr/search/config.json:25 -> meerqat/ir/search.py:146) over shards of >= 65,536 rows with at most 768
@@ -19,11 +19,9 @@ def _default_switches():
     lib = _lib.load()
     lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_SCAN, 1)
     lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_MIN_TILES, 0)
-    lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_WAVES, 8)
     yield
     lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_SCAN, 1)
     lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_MIN_TILES, 0)
-    lib.mq_knn_set_option(_lib.KNN_OPT_SMALL_WAVES, 8)
 
 
 def _index(X, metric=0, factory="Flat", screen=True, tie_order=None):
@@ -34,19 +32,12 @@ def _index(X, metric=0, factory="Flat", screen=True, tie_order=None):
 
 
 def _both_scans(idx, Q, k):
-    """(D, I) through the streaming kernel and through the tile kernel of the same index.  The streaming kernel has two
-    instances -- two waves per SIMD (round 5, csrc/knn_small8.inc: the default) and one (round 4, csrc/knn_small.inc) -- which
-    must agree bit for bit; the first one's results and statistics are returned."""
+    """(D, I) through the streaming kernel and through the tile kernel of the same index, and the streaming search's
+    statistics."""
     from viquae_amd import _lib
     assert idx.scan_kind(len(Q), k) == "stream"
-    assert _lib.load().mq_knn_get_option(_lib.KNN_OPT_SMALL_WAVES) == 8
     D1, I1 = idx.search_batch(Q, k)
     stats = idx.screen_stats(len(Q), k)
-    with _lib.knn_option(_lib.KNN_OPT_SMALL_WAVES, 4):
-        D4, I4 = idx.search_batch(Q, k)
-        stats4 = idx.screen_stats(len(Q), k)
-    assert np.array_equal(I4, I1) and np.array_equal(D4, D1) and stats4[0] == stats[0]
-    from viquae_amd import _lib
     with _lib.knn_option(_lib.KNN_OPT_SMALL_SCAN, 0):
         assert idx.scan_kind(len(Q), k) == "tile"
         D0, I0 = idx.search_batch(Q, k)
@@ -56,7 +47,7 @@ def _both_scans(idx, Q, k):
 @pytest.mark.parametrize("n,d,nq,k,metric", [
     (66000, 768, 256, 100, 0),    # the reference's shape (DPR, inner product)
     (65549, 768, 199, 100, 0),    # ragged: N not a multiple of 32, a partial query tile
-    (70000, 512, 64, 100, 0),     # CLIP width: the 8-K-block instance (ring of four tiles); one live wave
+    (70000, 512, 64, 100, 0),     # CLIP width: the 8-K-block instance (ring of four tiles); two of eight waves live
     (90000, 64, 21, 10, 0),       # one K block, ring of six
     (70001, 32, 200, 100, 0),     # one K block, all four waves live, both query halves (a bug of the first version: the second
     (65536, 3, 256, 1, 1),        #   half's first fragments were read from the NEXT ring slot) -- found by tools/stress_small_scan.py
@@ -87,9 +78,6 @@ def test_not_served_cases_keep_the_tile_kernel():
     assert ip.scan_kind(256, 129) == "tile"                                            # k beyond the fused selection
     assert ip.scan_kind(10, 300) == "tile" and ip.scan_kind(10, 1800) == "none"        # k beyond the screen: row ranges (round 4) / exact rounds
     assert l2.scan_kind(256, 100) == "stream"                                          # d = 768 + the two L2 columns = 13 K blocks: the row term travels as fp32 (round 6)
-    from viquae_amd import _lib
-    with _lib.knn_option(_lib.KNN_OPT_SMALL_WAVES, 4):
-        assert l2.scan_kind(256, 100) == "tile"                                        # ... by the two-waves-per-SIMD instance only
     assert l2.scan_kind(19, 100) == "none"                                             # FAISS's small-batch L2 form
     small = _index(X[:60000], 0)
     assert small.scan_kind(256, 100) == "tile"                                         # fewer than eight 32-row tiles per workgroup
@@ -128,7 +116,7 @@ def test_tie_heavy_data_overflows_the_pool_halves_and_falls_back():
 @pytest.mark.parametrize("copies", [40, 300])
 def test_runs_of_equal_rows_fill_pool_halves_beyond_their_first_line(copies):
     """Every row repeated `copies` times in a run: the slabs that hold a query's best rows take dozens (40 copies) to more than a
-    hundred (300 copies: a run is longer than a slab, and the k-th score is tied 300 ways) keys per lane half.  The two-waves
+    hundred (300 copies: a run is longer than a slab, and the k-th score is tied 300 ways) keys per lane half.  The streaming
     kernel fills a half front to back and cand_select_kernel reads its first 64-byte line directly, the lines behind it from a
     list in LDS (POOL_LAYOUT_HALVES); the answer must stay the exact scan's and the oracle's, without the fallback."""
     from oracle import knn as ok
@@ -238,17 +226,6 @@ def test_centred_queries_through_the_streaming_kernel(d, shift):
 # round 6: the L2 metric at d = 768 (13 K blocks of bf16 columns) through the streaming kernel -- the row term -||x||^2 / 2 enters
 # the accumulation chain as fp32 (csrc/knn_small8.inc, ROWTERM) instead of through two more columns
 # ---------------------------------------------------------------------------------------------------------------------
-def _stream_and_tile(idx, Q, k):
-    from viquae_amd import _lib
-    assert idx.scan_kind(len(Q), k) == "stream"
-    D1, I1 = idx.search_batch(Q, k)
-    stats = idx.screen_stats(len(Q), k)
-    with _lib.knn_option(_lib.KNN_OPT_SMALL_SCAN, 0):
-        assert idx.scan_kind(len(Q), k) == "tile"
-        D0, I0 = idx.search_batch(Q, k)
-    return (D1, I1), (D0, I0), stats
-
-
 @pytest.mark.parametrize("n,nq,k", [(66000, 256, 100), (65549, 199, 100), (131072, 20, 1), (70017, 64, 128), (200000, 256, 10)])
 def test_l2_at_768_columns_streams_and_equals_tile_scan_and_oracle(n, nq, k):
     from oracle import knn as ok
@@ -258,7 +235,7 @@ def test_l2_at_768_columns_streams_and_equals_tile_scan_and_oracle(n, nq, k):
     Q[0] = X[n // 3]                      # an exact copy: the clamp at distance 0
     X[n - 1] = Q[1] * np.float32(1.0001)  # the best row of a query is the shard's LAST row (ragged last tile when n % 32 != 0)
     idx = _index(X, 1)
-    (D1, I1), (D0, I0), stats = _stream_and_tile(idx, Q, k)
+    (D1, I1), (D0, I0), stats = _both_scans(idx, Q, k)
     assert np.array_equal(I1, I0) and np.array_equal(D1, D0)
     Do, Io = ok.knn(X, Q, k, metric=1)
     assert np.array_equal(I1, Io) and np.array_equal(D1, Do)
@@ -309,7 +286,7 @@ def test_centred_queries_at_768_columns_stream():
     Q = (mu + 0.25 * torch.randn((256, 768), generator=g, device="cuda")).cpu().numpy()
     idx = _index(X, 0)
     assert idx._screen_metric == METRIC_IP_CENTRED
-    (D1, I1), (D0, I0), stats = _stream_and_tile(idx, Q, 100)
+    (D1, I1), (D0, I0), stats = _both_scans(idx, Q, 100)
     assert np.array_equal(I1, I0) and np.array_equal(D1, D0)
     Do, Io = ok.knn(X, Q, 100)
     assert np.array_equal(I1, Io) and np.array_equal(D1, Do)

@@ -100,11 +100,12 @@ def test_phase_flags_through_the_c_abi():
     assert rc != 0
 
 
-@pytest.mark.parametrize("front,tail", [(8, 4), (4, 8)])
+@pytest.mark.parametrize("front,tail", [(1, 0), (0, 1)])
 def test_streaming_variant_switched_between_the_two_phases(front, tail):
-    """The two streaming scans leave their pools in different layouts (knn_screen.inc: POOL_LAYOUT_*); the scan records which in
-    the workspace.  A TAIL call whose host-side choice disagrees with what the FRONT call's scan left (MQ_KNN_OPT_SMALL_WAVES
-    changed in between) must notice and hand the tile to the exact scan -- same answer, never a walk of the wrong layout."""
+    """The streaming scan and the tile kernel leave their pools in different layouts (knn_screen.inc: POOL_LAYOUT_*); the scan
+    records which in the workspace.  A TAIL call whose host-side choice disagrees with what the FRONT call's scan left
+    (MQ_KNN_OPT_SMALL_SCAN changed in between) must notice and hand the tile to the exact scan -- same answer, never a walk of
+    the wrong layout."""
     import torch
     from viquae_amd import _lib
     from viquae_amd.index import FLAG_PHASE_FRONT, FLAG_PHASE_TAIL, MI355XFlatIndex
@@ -119,9 +120,9 @@ def test_streaming_variant_switched_between_the_two_phases(front, tail):
     spaces, _ = idx.pipeline_workspaces(200, 100)
     main = torch.cuda.current_stream()
     out = (torch.zeros_like(D), torch.zeros_like(I))
-    with _lib.knn_option(_lib.KNN_OPT_SMALL_WAVES, front):
+    with _lib.knn_option(_lib.KNN_OPT_SMALL_SCAN, front):
         idx.search_phase(Q, 100, out, spaces[1], FLAG_PHASE_FRONT, main)
-    with _lib.knn_option(_lib.KNN_OPT_SMALL_WAVES, tail):
+    with _lib.knn_option(_lib.KNN_OPT_SMALL_SCAN, tail):
         idx.search_phase(Q, 100, out, spaces[1], FLAG_PHASE_TAIL, main)
     torch.cuda.synchronize()
     assert torch.equal(out[0], D) and torch.equal(out[1], I)

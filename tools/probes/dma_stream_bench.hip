@@ -1,4 +1,4 @@
-// LDS-DMA streaming micro-benchmark behind csrc/knn_small.inc: what HBM rate does a ring of LDS-DMA pieces reach, by
+// LDS-DMA streaming micro-benchmark behind csrc/knn_small8.inc: what HBM rate does a ring of LDS-DMA pieces reach, by
 // ring granularity, depth and address pattern?  One 256-thread workgroup per CU, LDS fully used by the ring.
 //   hipcc --offload-arch=gfx950 -O3 tools/probes/dma_stream_bench.hip -o /tmp/dma_stream_bench && /tmp/dma_stream_bench
 #include <hip/hip_runtime.h>

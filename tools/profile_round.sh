@@ -21,7 +21,7 @@ timeout 400 rocprofv3 --kernel-trace --stats -d $O/exact_kt --output-format csv 
 timeout 400 rocprofv3 --pmc FETCH_SIZE -d $O/exact_fetch --output-format csv -- $BE > $O/exact_fetch.log 2>&1
 timeout 400 rocprofv3 --pmc WRITE_SIZE -d $O/exact_write --output-format csv -- $BE > $O/exact_write.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/enc --output-format csv -- python3 $R/tools/bench_encoders.py > $O/enc.log 2>&1
-# the reference's own call size: 256 queries per search (one query tile -> the streaming scan, csrc/knn_small.inc)
+# the reference's own call size: 256 queries per search (one query tile -> the streaming scan, csrc/knn_small8.inc)
 S="python3 $R/tools/small_batch_search.py 256 50"
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/nq256_kt --output-format csv -- $S > $O/nq256_kt.log 2>&1
 timeout 400 rocprofv3 --pmc FETCH_SIZE -d $O/nq256_fetch --output-format csv -- $S > $O/nq256_fetch.log 2>&1

@@ -1,4 +1,4 @@
-"""The one-query-tile streaming scan (csrc/knn_small.inc) against the 256 x 256 tile kernel, same process, same index:
+"""The one-query-tile streaming scan (csrc/knn_small8.inc) against the 256 x 256 tile kernel, same process, same index:
 results must be equal bit for bit; ms per search for both.
 python3 tools/small_scan_check.py [rows] [d] [metric] [nq list, comma separated] [k]"""
 import os, sys, time

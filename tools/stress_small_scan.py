@@ -1,4 +1,4 @@
-"""Randomised stress of the one-query-tile streaming scan (csrc/knn_small.inc) against the exact fp32 scan on the GPU: bit-equal
+"""Randomised stress of the one-query-tile streaming scan (csrc/knn_small8.inc) against the exact fp32 scan on the GPU: bit-equal
 scores and ids over shards of 65,536 ... 400,000 rows, 1 ... 256 queries, any d up to 768, k up to 128, both metrics, both
 "L2norm," arithmetics, both tie orders, clustered / duplicated / heavy-tailed / low-rank / sorted data.
 usage: python tools/stress_small_scan.py [n_cases] [first_seed]"""

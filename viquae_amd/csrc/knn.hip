@@ -50,7 +50,7 @@ void knn_opt_init() {
         g_knn_opt[MQ_KNN_OPT_SMALL_SCAN].store((e = getenv("MQ_KNN_SMALL")) ? (atoi(e) != 0) : 1);
         g_knn_opt[MQ_KNN_OPT_SMALL_MIN_TILES].store((e = getenv("MQ_KNN_SMALL_MIN_TILES")) ? atoi(e) : 0);  // 0: the built-in floor
         g_knn_opt[MQ_KNN_OPT_PARTITIONS].store((e = getenv("MQ_KNN_PARTITIONS")) ? (atoi(e) != 0) : 1);
-        g_knn_opt[MQ_KNN_OPT_SMALL_WAVES].store((e = getenv("MQ_KNN_SMALL_WAVES")) ? (atoi(e) == 4 ? 4 : 8) : 8);
+        g_knn_opt[MQ_KNN_OPT_SMALL_WAVES].store(8);  // retired: stored, read by nothing (include/meerqat_hip.h)
     });
 }
 inline int knn_opt(int key) {
@@ -999,7 +999,6 @@ __global__ __launch_bounds__(256) void shard_merge_big_kernel(const float* __res
 }
 
 #include "knn_screen.inc"
-#include "knn_small.inc"
 #include "knn_small8.inc"
 #include "knn_direct.inc"
 
@@ -1130,20 +1129,19 @@ Geometry geometry(int64_t N, int d, int nq, int k, int cus, int metric = -1) {
     return g;
 }
 
-// The streaming kernel for one query tile (knn_small.inc) serves a screened search when its geometry holds: one query tile,
+// The streaming kernel for one query tile (knn_small8.inc) serves a screened search when its geometry holds: one query tile,
 // one slab per stripe slot (S = 256 = TQ: the workgroup of slab s owns query s), at most 12 K blocks of queries in registers,
 // k within the stripe bound, and enough 32-row tiles per slab for the ring to pay.  MQ_KNN_OPT_SMALL_SCAN = 0 switches it off,
 // MQ_KNN_OPT_SMALL_MIN_TILES = <n> lowers the tiles-per-slab floor (tests) -- mq_knn_set_option.
 // `rowterm` (out): the L2 metric / the centred inner product whose two row-term columns sit alone in a 13th K block (d a multiple of 64, dp = d + 64 = 832):
-// the two-waves-per-SIMD kernel reads 12 K blocks and takes the term as fp32 (knn_small8.inc).
+// the kernel's ROWTERM instance reads 12 K blocks and takes the term as fp32.
 bool small_scan_serves(const Geometry& g, int64_t N, int d, int metric, int k, int* nkb_out = nullptr, bool* rowterm_out = nullptr) {
     const int enabled = knn_opt(MQ_KNN_OPT_SMALL_SCAN), floor_opt = knn_opt(MQ_KNN_OPT_SMALL_MIN_TILES);
     const int min_tiles = floor_opt > 0 ? floor_opt : SM_MIN_TILES_PER_SLAB;
     if (!enabled || g.nqt != 1 || g.S != TQ || g.ms != SMAX_SLOTS || g.sps != 1) return false;
     int nkb = screen_dp(d, metric) / SBK;
     bool rowterm = false;
-    if (nkb == SM_MAX_NKB + 1 && (metric == MQ_METRIC_L2 || metric == MQ_METRIC_IP_CENTRED) && d % SBK == 0 &&
-        knn_opt(MQ_KNN_OPT_SMALL_WAVES) == 8) {
+    if (nkb == SM_MAX_NKB + 1 && (metric == MQ_METRIC_L2 || metric == MQ_METRIC_IP_CENTRED) && d % SBK == 0) {
         nkb = SM_MAX_NKB;
         rowterm = true;
     }
@@ -1156,19 +1154,14 @@ bool small_scan_serves(const Geometry& g, int64_t N, int d, int metric, int k, i
 template <int NKB>
 int launch_small_scan_n(const SmallArgs& sa, int S, hipStream_t st) {
     constexpr int lds = sm_nst(NKB) * (NKB * SM_PIECE + 2 * SM_AUX) + 2 * TQ * 4 + SM_AUX;
-    if (knn_opt(MQ_KNN_OPT_SMALL_WAVES) == 8) {  // two waves per SIMD (knn_small8.inc)
-        if (NKB == SM_MAX_NKB && sa.rowterm) {  // the row term as fp32 beside 12 K blocks
-            constexpr int lds_rt = lds + sm_nst(SM_MAX_NKB) * SM_AUX;  // + the ring slots' row terms
-            MQ_DYNAMIC_LDS(lds_rt, screen_small8_kernel<SM_MAX_NKB, true>);
-            hipLaunchKernelGGL((screen_small8_kernel<SM_MAX_NKB, true>), dim3((unsigned)S), dim3(512), lds_rt, st, sa);
-            return MQ_OK;
-        }
-        MQ_DYNAMIC_LDS(lds, screen_small8_kernel<NKB>);
-        hipLaunchKernelGGL(screen_small8_kernel<NKB>, dim3((unsigned)S), dim3(512), lds, st, sa);
+    if (NKB == SM_MAX_NKB && sa.rowterm) {  // the row term as fp32 beside 12 K blocks
+        constexpr int lds_rt = lds + sm_nst(SM_MAX_NKB) * SM_AUX;  // + the ring slots' row terms
+        MQ_DYNAMIC_LDS(lds_rt, screen_small8_kernel<SM_MAX_NKB, true>);
+        hipLaunchKernelGGL((screen_small8_kernel<SM_MAX_NKB, true>), dim3((unsigned)S), dim3(512), lds_rt, st, sa);
         return MQ_OK;
     }
-    MQ_DYNAMIC_LDS(lds, screen_small_kernel<NKB>);
-    hipLaunchKernelGGL(screen_small_kernel<NKB>, dim3((unsigned)S), dim3(256), lds, st, sa);
+    MQ_DYNAMIC_LDS(lds, screen_small8_kernel<NKB>);
+    hipLaunchKernelGGL(screen_small8_kernel<NKB>, dim3((unsigned)S), dim3(512), lds, st, sa);
     return MQ_OK;
 }
 
@@ -1461,6 +1454,29 @@ static int launch_scan_m(bool xrow, bool ceil, const ScanArgs& a, hipStream_t st
 static int launch_scan(int metric, bool xrow, bool ceil, const ScanArgs& a, hipStream_t st) {
     return metric == MQ_METRIC_L2 ? launch_scan_m<MQ_METRIC_L2>(xrow, ceil, a, st) : launch_scan_m<MQ_METRIC_IP>(xrow, ceil, a, st);
 }
+
+// queries -> fp32 panel layout (+ the optional "L2norm," transform `form`, + ||q||^2) for the exact scan.  `only`: the flagged
+// query tiles alone.  `clear`: panels and norms are zeroed first and the pack covers the real queries; without it every panel of
+// the padded tiles is written, padding rows included (the screened tail: panels of flagged tiles only, no clearing launch in front).
+static int pack_query_panels(const Geometry& g, const float* q, int nq, int d, int form, const int* only, bool clear, float* Qp,
+                             float* qn, hipStream_t st) {
+    if (clear) MQ_HIP(hipMemsetAsync(Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, st));
+    const unsigned panels = clear ? (unsigned)((nq + PANEL - 1) / PANEL) : (unsigned)(g.nqpad / PANEL);
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(panels), dim3(256), 0, st, q, (int64_t)nq, d, g.dpad, (int64_t)0, form, Qp, qn, only,
+                       clear ? (int64_t)0 : (int64_t)g.nqpad);
+    MQ_HIP(hipGetLastError());
+    return MQ_OK;
+}
+
+// the exact scan's arguments over X (the panel copy, or the row-major copy) for the query panels Qp / qn
+static ScanArgs exact_scan_args(const Geometry& g, const float* X, const float* xn, const float* Qp, const float* qn, u64* lists,
+                                int64_t N, int d, int k, unsigned flip, const int* only, unsigned long long* dbg) {
+    ScanArgs a;
+    a.Xp = X; a.Qp = Qp; a.xn = xn; a.qn = qn; a.lists = lists; a.d = d;
+    a.N = N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.k = k; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = dbg; a.only = only;
+    a.flip = flip; a.ceil = nullptr;
+    return a;
+}
 extern "C" {
 static int launch_slab_merge(int metric, const u64* lists, int nq, int S, int k, int64_t id_offset, float* D_dev, int64_t* I_dev,
                              const int* only, unsigned flip, int kout, int col0, u64* next_ceil, hipStream_t st) {
@@ -1515,16 +1531,10 @@ static int knn_search_impl(const float* packed_dev, const float* sqnorm_dev, int
     if (metric == MQ_METRIC_L2 && nq < MQ_KNN_L2_DIRECT_BELOW)
         return knn_search_l2_direct(packed_dev, nullptr, N, d, queries_dev, nq, k, flags, id_offset, D_dev, I_dev, ws_dev, g, st);
 
-    // queries -> panel layout (+ optional "L2norm," transform, + ||q||^2); padded queries are zero
-    MQ_HIP(hipMemsetAsync(Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, st));
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((nq + PANEL - 1) / PANEL)), dim3(256), 0, st, queries_dev, (int64_t)nq, d,
-                       g.dpad, (int64_t)0, query_l2norm_form(flags), Qp, qn, (const int*)nullptr);
-    MQ_HIP(hipGetLastError());
-
-    ScanArgs a;
-    a.Xp = packed_dev; a.Qp = Qp; a.xn = sqnorm_dev; a.qn = qn; a.lists = lists;
-    a.N = N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.k = k; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = dbg_ptr(); a.only = nullptr; a.d = d;
-    a.flip = tie_flip(flags); a.ceil = nullptr;
+    // queries -> panel layout; padded queries are zero
+    if (const int rc = pack_query_panels(g, queries_dev, nq, d, query_l2norm_form(flags), nullptr, true, Qp, qn, st); rc != MQ_OK)
+        return rc;
+    const ScanArgs a = exact_scan_args(g, packed_dev, sqnorm_dev, Qp, qn, lists, N, d, k, tie_flip(flags), nullptr, dbg_ptr());
     if (N > 0)
         return exact_scan_rounds(metric, false, a, g, nq, k, id_offset, D_dev, I_dev, ws, nullptr, st, ev_scan_begin, ev_scan_end);
     MQ_HIP(hipMemsetAsync(lists, 0, (size_t)g.nqt * g.S * TQ * (size_t)POOL * 8, st));
@@ -1628,6 +1638,7 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
     const int dp = screen_dp(d, metric);
     // packed_dev may be NULL (an index that keeps no panel copy): the exact-scan fallback and FAISS's small-batch L2 form then
     // read the row-major copy
+    const float* const X = packed_dev ? packed_dev : rowmajor_dev;
     if (!sqnorm_dev || !rowmajor_dev || !bf16_dev || !xstats_dev || !queries_dev || !D_dev || !I_dev || !ws_dev)
         return MQ_EINVAL;
     if (N <= 0 || d <= 0 || nq < 0 || k <= 0) return MQ_EINVAL;
@@ -1691,39 +1702,24 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
                            (long long)pl.per, (long long)N, D_dev, (long long*)I_dev, pflags);
         MQ_HIP(hipGetLastError());
         // flagged tiles: the exact rounds (no-op otherwise: every workgroup of an unflagged tile returns at once)
-        MQ_HIP(hipMemsetAsync(Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, st));
-        hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((nq + PANEL - 1) / PANEL)), dim3(256), 0, st, q_rm, (int64_t)nq, d,
-                           g.dpad, (int64_t)0, 0, Qp, qn, (const int*)pflags);
-        MQ_HIP(hipGetLastError());
-        ScanArgs a;
-        a.Xp = packed_dev ? packed_dev : rowmajor_dev; a.Qp = Qp; a.xn = sqnorm_dev; a.qn = qn; a.lists = pools; a.d = d;
-        a.N = N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.k = k; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = nullptr; a.only = pflags;
-        a.flip = flip; a.ceil = nullptr;
-        return exact_scan_rounds(tm, packed_dev == nullptr, a, g, nq, k, id_offset, D_dev, I_dev, ws, pflags, st, nullptr, nullptr);
+        if (const int rc = pack_query_panels(g, q_rm, nq, d, 0, pflags, true, Qp, qn, st); rc != MQ_OK) return rc;
+        return exact_scan_rounds(tm, packed_dev == nullptr, exact_scan_args(g, X, sqnorm_dev, Qp, qn, pools, N, d, k, flip, pflags, nullptr),
+                                 g, nq, k, id_offset, D_dev, I_dev, ws, pflags, st, nullptr, nullptr);
     }
     if (k > SCREEN_MAX_K) {
         // More than SCREEN_MAX_K neighbours: the bounded screening buffers are sized for the reference's k = 100 (the pools hold
         // 512 survivors per slab, the stripe bound works on 256 slots: k <= 224 still goes through the screen, round 3); the exact
         // scan serves the call in ceil(k / 128) rounds (from the panel copy, or from the row-major copy of an index without one).
-        MQ_HIP(hipMemsetAsync(Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, st));
-        hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((nq + PANEL - 1) / PANEL)), dim3(256), 0, st, q_rm, (int64_t)nq, d,
-                           g.dpad, (int64_t)0, 0, Qp, qn, (const int*)nullptr);
-        MQ_HIP(hipGetLastError());
-        ScanArgs a;
-        a.Xp = packed_dev ? packed_dev : rowmajor_dev; a.Qp = Qp; a.xn = sqnorm_dev; a.qn = qn; a.lists = pools; a.d = d;
-        a.N = N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.k = k; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = nullptr; a.only = nullptr;
-        a.flip = flip; a.ceil = nullptr;
-        return exact_scan_rounds(tm, packed_dev == nullptr, a, g, nq, k, id_offset, D_dev, I_dev, ws, nullptr, st, ev_scan_begin,
-                                 ev_scan_end);
+        if (const int rc = pack_query_panels(g, q_rm, nq, d, 0, nullptr, true, Qp, qn, st); rc != MQ_OK) return rc;
+        return exact_scan_rounds(tm, packed_dev == nullptr, exact_scan_args(g, X, sqnorm_dev, Qp, qn, pools, N, d, k, flip, nullptr, nullptr),
+                                 g, nq, k, id_offset, D_dev, I_dev, ws, nullptr, st, ev_scan_begin, ev_scan_end);
     }
     if (do_front) {
     // The fp32 panel copy of the queries (+ ||q||^2) serves the exact-scan fallback -- and, for the L2 metric, the
     // re-scoring (||q||^2).  With the inner product it is made after the screened pipeline, for flagged tiles only.
     if (l2) {
-        MQ_HIP(hipMemsetAsync(Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, st));
-        hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)((nq + PANEL - 1) / PANEL)), dim3(256), 0, st, q_rm, (int64_t)nq, d,
-                           g.dpad, (int64_t)0, 0, Qp, qn, (const int*)nullptr);
-        MQ_HIP(hipGetLastError());
+        const int rc = pack_query_panels(g, q_rm, nq, d, 0, nullptr, true, Qp, qn, st);
+        if (rc != MQ_OK) return rc;
     }
     if (g.nqpad > nq)  // bf16 rows of the padding queries: the last tile (tile layout: its real rows are written below)
         MQ_HIP(hipMemsetAsync(Qb + (size_t)(g.nqpad - TQ) * dp, 0, (size_t)TQ * dp * 2, st));
@@ -1748,7 +1744,7 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
         int small_nkb = 0;
         bool small_rowterm = false;
         if (small_scan_serves(g, N, d, metric, k, &small_nkb, &small_rowterm)) {
-            // one query tile: the streaming kernel with the queries in registers (knn_small8.inc / knn_small.inc)
+            // one query tile: the streaming kernel with the queries in registers (knn_small8.inc)
             SmallArgs sa;
             sa.s = a;
             sa.ntiles = (N + SM_ROWS - 1) / SM_ROWS;
@@ -1777,15 +1773,12 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
         const int* layout_word = g.nqt == 1 ? (const int*)(ovf + 1) : (const int*)nullptr;
         const unsigned* gthr = (const unsigned*)(ws + g.off_gthr);
         const unsigned* smax = (const unsigned*)(ws + g.off_smax);
-        if (small_scan_serves(g, N, d, metric, k) && knn_opt(MQ_KNN_OPT_SMALL_WAVES) == 8)  // (checked against the word the scan left)
-            hipLaunchKernelGGL(cand_select_kernel<CSEL_WALK_HALVES>, dim3((unsigned)nq), dim3(256), 0, st, pools, pcount, margin, gthr,
-                               smax, g.ms, ovf, nq, g.S, k, cand, ccount, layout_word);
-        else if (g.S >= 64)
-            hipLaunchKernelGGL(cand_select_kernel<CSEL_WALK_SLICE_LINES>, dim3((unsigned)nq), dim3(256), 0, st, pools, pcount, margin, gthr,
-                               smax, g.ms, ovf, nq, g.S, k, cand, ccount, layout_word);
-        else
-            hipLaunchKernelGGL(cand_select_kernel<CSEL_WALK_SLICES>, dim3((unsigned)nq), dim3(256), 0, st, pools, pcount, margin, gthr,
-                               smax, g.ms, ovf, nq, g.S, k, cand, ccount, layout_word);
+        // (the walk is checked against the word the scan left)
+        const int walk = small_scan_serves(g, N, d, metric, k) ? CSEL_WALK_HALVES : (g.S >= 64 ? CSEL_WALK_SLICE_LINES : CSEL_WALK_SLICES);
+        const auto csel = walk == CSEL_WALK_HALVES ? cand_select_kernel<CSEL_WALK_HALVES>
+                          : walk == CSEL_WALK_SLICE_LINES ? cand_select_kernel<CSEL_WALK_SLICE_LINES> : cand_select_kernel<CSEL_WALK_SLICES>;
+        hipLaunchKernelGGL(csel, dim3((unsigned)nq), dim3(256), 0, st, pools, pcount, margin, gthr, smax, g.ms, ovf, nq, g.S, k, cand,
+                           ccount, layout_word);
     }
     MQ_HIP(hipGetLastError());
     hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)nq, RMAX / 64), dim3(256), 0, st, rowmajor_dev, q_rm, d, cand, ccount, ckeys,
@@ -1801,16 +1794,12 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
     // 5. query tiles whose bounded buffers overflowed are recomputed by the exact scan (no-op otherwise:
     //    every workgroup of an unflagged tile returns at once)
     {
-        if (!l2) {  // (panels of flagged tiles only, their padding rows included: no clearing launch in front)
-            hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)(g.nqpad / PANEL)), dim3(256), 0, st, q_rm, (int64_t)nq, d,
-                               g.dpad, (int64_t)0, 0, Qp, qn, (const int*)ovf, (int64_t)g.nqpad);
-            MQ_HIP(hipGetLastError());
+        if (!l2) {  // (the L2 panels were made in front of the screen)
+            const int rc = pack_query_panels(g, q_rm, nq, d, 0, ovf, false, Qp, qn, st);
+            if (rc != MQ_OK) return rc;
         }
-        ScanArgs a;
-        a.Xp = packed_dev ? packed_dev : rowmajor_dev; a.Qp = Qp; a.xn = sqnorm_dev; a.qn = qn; a.lists = pools; a.d = d;
-        a.N = N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.k = k; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = nullptr; a.only = ovf;
-        a.flip = flip; a.ceil = nullptr;
-        const int rc = exact_scan_rounds(tm, packed_dev == nullptr, a, g, nq, k, id_offset, D_dev, I_dev, ws, ovf, st, nullptr, nullptr);
+        const int rc = exact_scan_rounds(tm, packed_dev == nullptr, exact_scan_args(g, X, sqnorm_dev, Qp, qn, pools, N, d, k, flip, ovf, nullptr),
+                                         g, nq, k, id_offset, D_dev, I_dev, ws, ovf, st, nullptr, nullptr);
         if (rc != MQ_OK) return rc;
     }
     return MQ_OK;

@@ -1,21 +1,48 @@
-// knn_small8.inc -- the streaming screening scan for ONE query tile with TWO waves per SIMD (round 5), included by knn.hip after
-// knn_small.inc, whose data flow it keeps: queries in registers for the whole launch, the whole LDS a ring of 32-row tiles of the
-// bf16 copy filled by LDS-DMA two tiles ahead, one workgroup per CU = one slab, every row read from HBM once, the same stripe
-// maxima / gthr bounds / candidate pools behind it (cand_select / rescore / final_select: bit-identical search results).
+// knn_small8.inc -- the streaming screening scan for ONE query tile (<= 256 queries), included by knn.hip after knn_screen.inc.
 //
-// What changes is who hides what.  screen_small_kernel keeps a wave's 64 queries x 768 columns in 384 of the 512 registers of a
-// SIMD lane: ONE wave per SIMD, which issues in order -- whatever stands between two MFMAs beyond 2-3 instructions (the selection's
-// hit blocks ~1000 cycles per item, bookkeeping 450-640, barrier skew 500-800: profiles/r04_notes.md section 4) is idle matrix
-// pipe, and round 4 measured 6450 cycles per 32-row item against 3260 of MFMAs.  Here a workgroup has EIGHT waves, two per SIMD:
-// wave w owns queries [32 w, 32 w + 32) -- NKB x 16 accumulation registers per lane (192 at dp = 768), ONE 32 x 32 accumulator --
-// and does 4 NKB MFMAs per item over the same 32 rows.  Same MFMA count and same LDS read traffic per CU (eight waves read every A
-// fragment once; there: four waves twice), but while one wave of a SIMD selects, appends, publishes or waits at the barrier, the
-// other one's MFMAs keep the matrix pipe busy -- the ordinary latency hiding the 16-wave tile kernel has, without its query traffic.
-// No hand-placed riders: the selection is plain code after the item's MFMAs.
+// The reference searches in `Dataset.map` batches of 256 questions (experiments/ir/viquae/dpr/search/config.json:25 ->
+// meerqat/ir/search.py:146): one query tile.  screen_scan_kernel then streams the bf16 copy of the shard exactly once, and
+// the work is balanced between HBM (2.3 GB at 1.5M x 768) and the matrix pipe (0.59 TFLOP): it has to be a STREAMING kernel.
+// The 256 x 256 tile kernel is not: it re-fetches the query tile every K step through the same LDS-DMA queue as the rows
+// (as many L2 -> LDS bytes as HBM -> LDS bytes) and its two 64-KiB stages leave one step of lookahead for an HBM round
+// trip (0.73-0.755 ms = 3.1 TB/s).  This kernel turns the roles around:
+//
+//   * the QUERIES live in registers for the whole launch: eight waves per workgroup, two per SIMD; wave w owns queries
+//     [32 w, 32 w + 32) as the B operands of v_mfma_f32_32x32x16_bf16 for every k (register budget below) and does 4 NKB
+//     MFMAs per item = one 32-row tile into ONE 32 x 32 accumulator;
+//   * the whole LDS (160 KiB) is a ring of NST row tiles of [32 rows][dp] bf16 (48 KiB at dp = 768, NST = 3), filled by
+//     LDS-DMA two tiles ahead (tools/probes/dma_stream_bench.hip: this ring alone streams 6.3 TB/s), no query traffic
+//     at all, ONE barrier per item;
+//   * 256 workgroups = 256 slabs of consecutive row tiles, one workgroup per CU, each row read from HBM exactly once.
+//
+// Why two waves per SIMD: a wave issues in order, and whatever stands between two of its MFMAs beyond 2-3 instructions (the
+// selection's appends, the bookkeeping, barrier skew) is idle matrix pipe when it is alone on its SIMD.  With two, while one wave
+// selects, appends, publishes or waits at the barrier, the other one's MFMAs keep the matrix pipe busy -- the ordinary latency
+// hiding the 16-wave tile kernel has, without its query traffic.  No hand-placed riders: the selection is plain code after the
+// item's MFMAs.  (Round 4's one-wave-per-SIMD kernel and its cycle accounting: DESIGN_HISTORY.md, profiles/r04_notes.md.)
+//
+// Selection is the tile kernel's, re-mapped: a lane column of the 32 x 32 accumulator is one query, so thresholds are
+// lane-local; every (lane half, slab) is one stripe of disjoint rows whose running maximum is published into the
+// query's slot of the slab (atomic max); the workgroup of slab s owns query s of the tile: it turns the 256 slot maxima
+// of that query into a lower bound of the global k-th best S~ (k-th largest slot) and publishes it in gthr[s].
+// Inside the streaming loop nothing is read from global memory by an instruction the compiler would wait for (a
+// compiler-issued load waits with vmcnt(0) = a drained DMA ring; so does the reload of a spilled register, which is why
+// every per-lane offset of a rare path is re-derived from the thread id there): the slot row of the owned query and the
+// 256 gthr words arrive through the same LDS-DMA queue as the rows, one 1-KiB aux piece each per tile (waves 1 and 0), with
+// the sc1 policy, and are consumed one ring turn later.  The first items of a slab are a warm-up: scored for the stripe
+// maxima only (threshold +inf), and scored again at the END of the slab.
+// Appends go to the lane's own half of the (query, slab) pool (512 slots = slices 4 kg .. 4 kg + 3 of the pool layout
+// cand_select_kernel reads), filled front to back: POOL_LAYOUT_HALVES, recorded in the workspace word behind the tile's
+// overflow flag.  A half that fills up flags the tile for the exact scan (tie-heavy data only: a slab pool receives ~10 keys).
+//
+// Same keys, same pools, same cand_select / rescore / final_select behind it: the search result is bit-identical to
+// the tile kernel's and to the exact scan's (tests/test_small_scan_gpu.py).
 //
 // Register budget: 512 per SIMD lane / 2 waves = 256 per wave = 16 NKB accumulation registers (queries, named as MFMA B operands
-// in asm: "a" constraints) + at most 256 - 16 NKB VGPRs: 64 at NKB = 12 (accumulator 16, ring of four A fragments 16, fragment
-// addresses 4, selection state) -- the kernel must not spill: a scratch reload inside the streaming loop is a vmcnt(0), a drained ring.
+// in asm: "a" constraints -- the unified register file of gfx950 lets A / B operands be accumulation registers; the compiler on
+// its own copies them to VGPRs first) + at most 256 - 16 NKB VGPRs: 64 at NKB = 12 (accumulator 16, ring of four A fragments 16,
+// fragment addresses 4, selection state) -- the kernel must not spill: a scratch reload inside the streaming loop is a vmcnt(0),
+// a drained ring.
 //
 // The L2 metric -- and the centred inner product -- at d = 768 (round 6; round 5's attempts: tools/probes/small8_l2_rowterm.patch).  Its row term -||x||^2 / 2 sits in
 // two extra bf16 columns = a 13th K block, one more than the registers hold.  When those two columns are ALONE in their block (d a
@@ -30,6 +57,52 @@
 // LDS-DMA: all NKB pieces of a tile ([32 rows][128 B] each) are issued by the four waves of group 0 (w < 4; group = w >> 2), eight
 // rows each, one instruction per piece and wave; the late waves 4-7 issue nothing (issue_all).  The aux pieces (gthr words, the
 // owned query's stripe slots) stay with waves 0 and 1.
+
+constexpr int SM_ROWS = 32;                  // KB rows per ring tile
+constexpr int SM_PIECE = SM_ROWS * SBK * 2;  // [32 rows][64 k] bf16 = 4 KiB: one contiguous piece of the tiled bf16 copy
+constexpr int SM_MAX_NKB = 12;               // dp <= 768: 12 K blocks x 16 = 192 of a wave's 256 registers per lane hold its queries
+constexpr int SM_AUX = 1024;                 // one aux piece (256 words) per ring slot and kind
+constexpr int SM_MIN_TILES_PER_SLAB = 8;     // below that the tile kernel serves the search
+constexpr int SM_HALF = SPOOL / 2;           // pool slots of one lane half
+// ring depth: NST x (tile + two aux pieces) + thr / marg / scratch (3 KiB) within 160 KiB, at most 6
+constexpr int sm_nst(int nkb) { return (157 * 1024) / (nkb * SM_PIECE + 2 * SM_AUX) > 6 ? 6 : (157 * 1024) / (nkb * SM_PIECE + 2 * SM_AUX); }
+
+struct SmallArgs {
+    ScreenArgs s;
+    long long ntiles;   // 32-row tiles of the shard
+    const float* sqn;   // screen_small8_kernel<12, true> only: ||x||^2 per row (L2: the row term -||x||^2 / 2 travels as fp32), or NULL with
+                        // `rowterm` set: the term is read as the (h, l) pair of the copy's 13th K block (centred inner product)
+    int rowterm;        // 0: the plain instance; 1: the ROWTERM instance
+    int nkb_copy;       // K blocks of the stored bf16 copy per 256-row block (= the kernel's NKB, + 1 with the fp32 row term)
+};
+
+// dma16s with the sc1 policy: the aux pieces
+__device__ __forceinline__ void dma16s_sc1(const void* sbase, unsigned voff, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
+
+template <int N>
+__device__ __forceinline__ void sm_wait_vm() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
+}
+
+// D = A(x rows) . B(queries) + C on the bf16 matrix pipe with the B operand in an accumulation register / a VGPR.
+// `s_nop 1`: the A operand may have been written by a VALU move the compiler placed right in front of the statement.
+// The accumulator lives in VGPRs: the selection reads it as ordinary VALU operands (in accumulation registers every score
+// would cost a v_accvgpr_read first).
+#define SM_MFMA_A(acc, xa, qb) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(xa), "a"(qb))
+#define SM_MFMA_V(acc, xa, qb) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(xa), "v"(qb))
+#define SM_MFMA_A0(acc, xa, qb) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(xa), "a"(qb))
+
+#ifdef MQ_TIMING
+// cycle accounting per wave (tools/small_scan_timing.py; the slots are listed in the kernel)
+#define SM_T(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc_[i] += now_ - tlast_; tlast_ = now_; }
+#else
+#define SM_T(i)
+#endif
 
 #ifndef SM8_NXF
 #define SM8_NXF(nkb) ((nkb) > 8 ? 4 : 6)
@@ -90,7 +163,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     if (tid < 8) wflag[tid] = 1u;
 
-    // ---- LDS-DMA (see knn_small.inc): the 16-byte chunk c of row r of a piece is stored at chunk c ^ ((r >> 1) & 7)
+    // ---- LDS-DMA: ring slot of item j = j % NST.  Early wave wr moves rows [8 wr, 8 wr + 8) of every piece, one instruction per
+    // piece -- the 16-byte chunk c of row r is stored at chunk c ^ ((r >> 1) & 7) (the fragment reads below are then bank-conflict
+    // free); the swizzle is applied to the SOURCE chunk.
     const int r8 = lane >> 3, ch = lane & 7;
     const unsigned voff = (unsigned)((8 * wr + r8) * 128 + ((ch ^ (((8 * wr + r8) >> 1) & 7)) * 16));
     const unsigned lds_ring = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + (unsigned)(wr * 1024);
@@ -105,9 +180,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto src_of = [&](const long long tile) { return xbase0 + (size_t)(tile >> 3) * blk_bytes + (size_t)(tile & 7) * SM_PIECE; };
     auto issue_all = [&](const char* src, const int slot) __attribute__((always_inline)) {  // this wave's share of one item, at once
         if (grp != 0) return;  // the late waves issue nothing (below)
-#if defined(SM8_ABL) && (SM8_ABL & 2)
-        if (slot >= 0) { sm_wait_vm<0>(); return; }  // ablation probe (timing only, wrong results): no LDS-DMA
-#endif
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb) dma16s(src + (size_t)kb * S_OP_BYTES, voff, lds_ring + slot * STAGE + kb * SM_PIECE);
         if (w == 0) dma16s_sc1(gthr_src, (unsigned)lane * 16u, lds_auxg + slot * SM_AUX);
@@ -222,11 +294,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 if (kb < QA) qa[kb * 4 + m] = v; else qv[(kb - QA) * 4 + m] = v;
             }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): also tells the compiler its own loads are back (knn_small.inc)
+    // vmcnt(0): the explicit wait also tells the compiler that its own loads (the queries) have returned -- without it, it waits
+    // for them at their first use INSIDE the loop, with counts that ignore the LDS-DMA pieces in flight: a drained ring every tile
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();                     // thr / marg
 
     // pool / slot offsets of the lane are re-derived from an opaque thread id where a rare path needs them: a loop invariant that
-    // does not fit the registers is spilled, and a scratch reload inside the streaming loop drains the LDS-DMA ring (knn_small.inc)
+    // does not fit the registers is spilled, and a scratch reload inside the streaming loop drains the LDS-DMA ring
     auto lane_q = [&]() __attribute__((always_inline)) {
         unsigned t_ = threadIdx.x;
         asm volatile("" : "+v"(t_));
@@ -248,10 +322,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // appends.  +inf while the item is a warm-up tile; a pool half that could not take 16 more scores stops taking any (flagged
     // at the end of the kernel).
     auto select = [&](const int js) __attribute__((always_inline)) {
-#if defined(SM8_ABL) && (SM8_ABL & 1)
-        asm volatile("" :: "v"(acc));  // ablation probe (timing only, wrong results): no selection at all
-        return;
-#endif
         const long long tile_s = tile_of(js);
         const unsigned rbs = (unsigned)(tile_s * SM_ROWS) + lane_kg4();
         const float t = (warm_end < 0 || js < warm_end || n > SM_HALF - 16) ? INFINITY : thr[lane_q()];
@@ -363,13 +433,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             // MFMAs -- each wave's selection, appends and bookkeeping overlap the other one's MFMAs instead of coinciding with its own
             // twin's (both waves leave the barrier together: in step, the matrix pipe idled through both selections)
             if (grp == 0) {
-#ifdef SM8_PRIO
-                __builtin_amdgcn_s_setprio(2);  // the wave in its MFMAs wins the issue arbitration over its twin's selection
-#endif
                 mfmas();
-#ifdef SM8_PRIO
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 // the accumulator is read by VALU instructions next: 16-pass MFMA -> 18 wait states
                 asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));
                 SM_T(5)
@@ -386,13 +450,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             } else {
                 if (j > 0) select(j - 1);
                 SM_T(3)
-#ifdef SM8_PRIO
-                __builtin_amdgcn_s_setprio(2);
-#endif
                 mfmas();
-#ifdef SM8_PRIO
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 SM_T(5)
                 bookkeeping();
                 SM_T(2)

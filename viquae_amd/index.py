@@ -580,7 +580,7 @@ class MI355XFlatIndex(BaseIndex):
 
     def scan_kind(self, nq, k):
         """Which screening scan serves a ``search_device`` call of ``nq`` queries: "tile" (256 x 256 tiles), "stream" (one query
-        tile, queries in registers: csrc/knn_small.inc) or "none" (exact rounds / FAISS's small-batch L2 form / exact index)."""
+        tile, queries in registers: csrc/knn_small8.inc) or "none" (exact rounds / FAISS's small-batch L2 form / exact index)."""
         if not self.screen or not self.ntotal:
             return "none"
         kind = int(_lib.load().mq_knn_screen_scan_kind(self.ntotal, self.d, int(nq), int(k), self._screen_metric))
