@@ -635,6 +635,39 @@ int mq_conv3x3_pair_f32(const uint16_t *Xh_dev, const uint16_t *Xl_dev, int B, i
 int mq_stem_conv3x3_f32(const float *x_dev, int B, int H, int W, const float *wt_dev, const float *bias_dev,
                         const float *prelu_slope_dev, const float *scale_dev, const float *shift_dev, uint16_t *Ph_dev,
                         uint16_t *Pl_dev, uint16_t *Dh_dev, uint16_t *Dl_dev, void *stream);
+/* ---- fp16 mode of the face encoder: the reference's autocast precision (arcface_torch `get_model('r50', fp16=True)`) ----
+ * Every tensor of the trunk is fp16, NHWC, in PAIR LAYOUT over [pixels, channels] (ONE array: 64-byte rows of 32 channels, rows padded
+ * to 256; mq_split_bf16_tiled_elems(rows, C) elements).  r(v) = round to fp16, nearest even, overflow to +-inf (Tensor.half()).  The
+ * BatchNorm behind a convolution is NOT folded: post_scale / post_shift [N] fp32 apply to r(acc), as autocast rounds the conv output
+ * before the BatchNorm.  PReLU slopes must hold fp16 values (r(slope)); BatchNorm scale / shift are fp32.
+ * mq_conv3x3_f16: 3 x 3, padding 1, stride 1 or 2, fp16 operands, one v_mfma_f32_32x32x16_f16 per 16 k, fp32 accumulation.
+ *   X_dev         fp16 input [B * H * W, C] (C a multiple of 32); Wt_dev fp16 weights [N, 9 C] (column (kh * 3 + kw) * C + c) in the
+ *                 tile layout of mq_split_bf16_tiled_f32 ([ceil(N / 256)][9 C / 32][256][32], zero rows beyond N; N a multiple of 64)
+ *   t = r(r(acc) * post_scale + post_shift)
+ *   prelu_slope_dev != NULL:  P = r(prelu(t))                                        (residual, Y, scale, shift must be NULL)
+ *   prelu_slope_dev == NULL:  Y = r(t + residual) (fp16 [M, N]: the next shortcut), and, when scale_dev / shift_dev [N] are given,
+ *                 P = r(Y * scale + shift) (the next block's bn1)
+ *   tile          as for mq_conv3x3_pair_f32 (MQ_CONV_TILE_PATCH_256x64 needs MQ_CONV_K_CHANNEL_MAJOR); AUTO takes the patch tile
+ *                 for N = 64 at stride 1 with MQ_CONV_K_CHANNEL_MAJOR
+ * mq_stem_conv3x3_f16: the stem (3 -> 64, 3 x 3, stride 1, padding 1) on the vector ALU: r(x) * wt (wt fp32 [27, 64] holding the
+ *   fp16 weights, row (kh * 3 + kw) * 3 + c), fp32 accumulation; v = r(prelu(r(r(acc) * post_scale + post_shift)));
+ *   P = r(v * scale + shift) [B * H * W, 64] (the first block's bn1);  D = v at even (h, w) [B * H/2 * W/2, 64] (D may be NULL).
+ *   W a multiple of 4, H even when D is asked for.
+ * mq_conv1x1_f16: 1 x 1, stride 1 or 2, no padding: Y = r(r(conv) * post_scale + post_shift) [B * Ho * Wo, N];  Wt_dev fp16
+ *   ROW-MAJOR [N, C]; C a multiple of 32, N a multiple of 64.
+ * mq_head_prep_f16: A[b, (h W + w) C + c] = split(r(X[b, h, w, c] * scale + shift)) -- bn2 - flatten (NHWC order) - .float() -- as
+ *   the bf16 (hi, lo) pair of mq_gemm_nt_bf16x3s_splitk_f32 (PAIR LAYOUT over [B, HW * C]); exact: an fp16 value is hi + lo. */
+int mq_conv3x3_f16(const uint16_t *X_dev, int B, int H, int W, int C, int stride, const uint16_t *Wt_dev, int N,
+                   const float *post_scale_dev, const float *post_shift_dev, const float *prelu_slope_dev,
+                   const uint16_t *residual_dev, const float *scale_dev, const float *shift_dev, uint16_t *Y_dev,
+                   uint16_t *P_dev, const void *zeros_dev, int tile, void *stream);
+int mq_stem_conv3x3_f16(const float *x_dev, int B, int H, int W, const float *wt_dev, const float *post_scale_dev,
+                        const float *post_shift_dev, const float *prelu_slope_dev, const float *scale_dev,
+                        const float *shift_dev, uint16_t *P_dev, uint16_t *D_dev, void *stream);
+int mq_conv1x1_f16(const uint16_t *X_dev, int B, int H, int W, int C, int stride, const uint16_t *Wt_dev, int N,
+                   const float *post_scale_dev, const float *post_shift_dev, uint16_t *Y_dev, void *stream);
+int mq_head_prep_f16(const uint16_t *X_dev, int B, int HW, int C, const float *scale_dev, const float *shift_dev,
+                     uint16_t *Ah_dev, uint16_t *Al_dev, void *stream);
 int mq_warp_affine_faces_f32(const uint8_t *images_dev, const int64_t *offsets_dev, const int32_t *hw_dev,
                              const int32_t *face_image_dev, const double *minv_dev, int nfaces, int size, float *out_dev,
                              void *stream);

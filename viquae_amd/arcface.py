@@ -23,17 +23,41 @@ input lines back to back, +6 % from L2 hits alone; with ``MQ_CONV_KORDER=tap`` i
 forwards agree bit for bit (tests/test_arcface_gpu.py), otherwise within fp32 rounding.
 
 Parity: arcface_torch is not vendored by the reference and not installable here -- ``oracle/arcface.py`` restates the PUBLISHED
-definition (parity unpinned); ``tests/test_arcface_gpu.py`` holds this module to that oracle within 1e-3."""
+definition (parity unpinned); ``tests/test_arcface_gpu.py`` holds this module to that oracle within 1e-3.
+
+``precision="fp16"`` (opt-in) runs the trunk at the reference's own precision, ``get_model('r50', fp16=True)``: fp16 autocast up to
+``flatten``, the head in fp32.  Every activation is ONE fp16 tensor (not a bf16 pair), every 3 x 3 convolution one
+``v_mfma_f32_32x32x16_f16`` per 16 k instead of three bf16 products, and the rounding points are autocast's: the convolution's
+output is rounded BEFORE its BatchNorm, so nothing is folded -- each convolution keeps its fp16 weights and its BatchNorm as an
+affine of the epilogue (``mq_conv3x3_f16``, ``mq_stem_conv3x3_f16``, ``mq_conv1x1_f16``; ``mq_head_prep_f16`` hands bn2's fp16
+output to the unchanged fp32-class head GEMM).  tests/test_arcface_fp16_gpu.py pins each kernel against a torch restatement of
+those rounding points (tests/autocast_schedule.py)."""
 import os
 
 import numpy as np
 import torch
 
 from . import _lib
-from .encoders import EPI_BIAS, EPI_BIAS_RESIDUAL, SplitAct, _HipEncoder, _check_cuda, _stream, gemm_nt, split_bf16_tiled
+from .encoders import EPI_BIAS, EPI_BIAS_RESIDUAL, SplitAct, _HipEncoder, _check_cuda, _stream, _tile, gemm_nt, split_bf16_tiled
 
 EPS = 1e-5
 LAYERS = (3, 4, 14, 3)
+PRECISIONS = ("fp32", "fp16")
+
+
+def _half(a):
+    """float array -> the same values rounded to fp16 (round to nearest even, as Tensor.half()), as float32"""
+    return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
+
+
+def _f16_bits(a):
+    """float array -> its fp16 values as an int16 tensor (the bits)"""
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32).astype(np.float16)).view(np.int16))
+
+
+def f16_empty(rows, channels, device):
+    """an fp16 activation [rows, channels] in PAIR LAYOUT (one array, rows padded to 256), as flat int16"""
+    return torch.empty(((rows + 255) // 256) * 256 * channels, dtype=torch.int16, device=device)
 
 
 def _affine(state, name):
@@ -69,8 +93,11 @@ class ArcFaceR50(_HipEncoder):
     image_size = 112
     num_features = 512
 
-    def __init__(self, state, layers=LAYERS, chunk=656):
+    def __init__(self, state, layers=LAYERS, chunk=656, precision="fp32"):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
         # chunk = faces per forward: the 14 x 14 stage (half the FLOPs) runs ceil(faces * 196 / 256) workgroups of one 256-row tile
         # each -- 328 faces = 252 of the 256 CUs in one round, 656 = 503 in two (256 faces: 196 of 256; measured 19.3 k -> 21.3 k
         # faces/s at 328 with the first implicit kernel; 23.8 k / 24.7 k at 328 / 656 with the final one)
@@ -113,10 +140,44 @@ class ArcFaceR50(_HipEncoder):
         self._reg("fc.w2", torch.from_numpy((wfc * fa[:, None]).astype(np.float32)))
         self._reg("fc.b", torch.from_numpy((np.asarray(state["fc.bias"], np.float64) * fa + fb).astype(np.float32)))
         self.num_features = wfc.shape[0]
+        if precision == "fp16":
+            self._init_f16(state)
+
+    def _init_f16(self, state):
+        """fp16 mode: the UNFOLDED weights rounded to fp16 and, per convolution, the BatchNorm behind it as (scale, shift) -- autocast
+        rounds the convolution's output before the BatchNorm reads it; PReLU slopes rounded to fp16 (autocast casts them)."""
+        def raw(name, t):  # int16 bits as they are (_reg would convert to fp32)
+            self.register_buffer(name.replace(".", "_"), t.contiguous(), persistent=False)
+
+        def bn(name, post):
+            a, b = _affine(state, post)
+            self._reg(name + ".ps", torch.from_numpy(a.astype(np.float32)))
+            self._reg(name + ".pb", torch.from_numpy(b.astype(np.float32)))
+
+        def conv3x3(name, post):
+            w = np.asarray(state[name + ".weight"], np.float32)            # [Cout, Cin, 3, 3] -> [Cout, (kh, kw, cin)]
+            raw(name + ".w16", _tile(_f16_bits(w.transpose(0, 2, 3, 1).reshape(w.shape[0], -1))))
+            bn(name, post)
+
+        w = np.asarray(state["conv1.weight"], np.float32)                  # the stem: [27, 64], row (kh * 3 + kw) * 3 + c
+        self._reg("conv1.wt16", torch.from_numpy(np.ascontiguousarray(_half(w.transpose(2, 3, 1, 0).reshape(27, -1)))))
+        bn("conv1", "bn1")
+        self._reg("prelu16", torch.from_numpy(_half(state["prelu.weight"])))
+        for s, n in enumerate(self.layers, start=1):
+            for i in range(n):
+                p = f"layer{s}.{i}"
+                conv3x3(p + ".conv1", p + ".bn2")
+                self._reg(p + ".prelu16", torch.from_numpy(_half(state[p + ".prelu.weight"])))
+                conv3x3(p + ".conv2", p + ".bn3")
+                if i == 0:
+                    w = np.asarray(state[p + ".downsample.0.weight"], np.float32)
+                    raw(p + ".downsample.0.w16", _f16_bits(w.reshape(w.shape[0], -1)))   # row-major [Cout, Cin]
+                    bn(p + ".downsample.0", p + ".downsample.1")
 
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_state_dict(cls, state, **kw):
+        """``kw``: ``layers``, ``chunk``, ``precision`` ("fp32", the default, or "fp16")"""
         return cls(state, **kw)
 
     @classmethod
@@ -192,6 +253,10 @@ class ArcFaceR50(_HipEncoder):
         walk 784 K steps (1.65 ms of a 15-ms forward), so the K range is split over 49 workgroup rows and the fp32 partials summed
         (mq_gemm_nt_bf16x3s_splitk_f32; MQ_ARCFACE_HEAD_SPLITS=1: the one-pass GEMM)."""
         A = self._im2col(y, B, H, W, 512, False, H, W, 1, 0, H * W * 512, None, self._v("head.pre_scale"), self._v("head.pre_shift"))
+        return self._fc(A, y)
+
+    def _fc(self, A, y):
+        """fc - features on the split pair A [B, 25088] of bn2's output (y: any tensor on the device and stream)"""
         nsplit = int(os.environ.get("MQ_ARCFACE_HEAD_SPLITS", "49"))
         if nsplit <= 1:
             return gemm_nt(A, self.fc_w2, bias=self.fc_b, epilogue=EPI_BIAS, wsplit=self._wsplit("fc.w2"))
@@ -217,6 +282,8 @@ class ArcFaceR50(_HipEncoder):
         return self._forward(x)
 
     def _forward(self, x):
+        if self.precision == "fp16":
+            return self._forward_f16(x)
         if os.environ.get("MQ_ARCFACE_CONV", "implicit") == "im2col":
             return self._forward_im2col(x)
         B, H, W = x.shape[0], self.image_size, self.image_size
@@ -269,3 +336,67 @@ class ArcFaceR50(_HipEncoder):
                 y, Ho, Wo = self._conv(p + ".conv2", o1, B, H, W, slope=self._v(p + ".prelu"), residual=identity)
                 H, W, pending = Ho, Wo, None
         return self._head(y, B, H, W)
+
+    # ------------------------------------------------------------------ fp16 (the reference's autocast precision)
+    def _b(self, name):
+        return getattr(self, name.replace(".", "_"))
+
+    def _zeros(self, dev):
+        zeros = self.__dict__.setdefault("_zero_pages", {})
+        if dev not in zeros:
+            zeros[dev] = torch.zeros(64, dtype=torch.uint8, device=dev)
+        return zeros[dev]
+
+    def _conv3x3_f16(self, name, xin, B, H, W, slope=None, residual=None, scale=None, shift=None, tile=0):
+        """mq_conv3x3_f16 of ``name`` on the fp16 activation ``xin`` [B * H * W, Cin].  ``slope``: -> P = r(prelu(t)).  Otherwise:
+        -> (Y = r(t + residual), P = r(Y * scale + shift) or None)."""
+        lib = _lib.load()
+        c = self._convs[name]
+        Ho, Wo = (H - 1) // c.stride + 1, (W - 1) // c.stride + 1
+        M, dev = B * Ho * Wo, xin.device
+        P = f16_empty(M, c.cout, dev) if (slope is not None or scale is not None) else None
+        Y = f16_empty(M, c.cout, dev) if slope is None else None
+        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        with torch.cuda.device(dev):
+            _lib.check(lib.mq_conv3x3_f16(xin.data_ptr(), B, H, W, c.cin, c.stride, self._b(name + ".w16").data_ptr(), c.cout,
+                                          self._b(name + ".ps").data_ptr(), self._b(name + ".pb").data_ptr(), p(slope), p(residual),
+                                          p(scale), p(shift), p(Y), p(P), self._zeros(dev).data_ptr(), int(tile) | 0x100, _stream(xin)),
+                       "mq_conv3x3_f16")
+        return (P if slope is not None else (Y, P)), Ho, Wo
+
+    def _forward_f16(self, x):
+        """The trunk at autocast's rounding points, one fp16 tensor per activation; the head fp32-class on bn2's fp16 output."""
+        lib = _lib.load()
+        B, H, W, dev = x.shape[0], self.image_size, self.image_size, x.device
+        blocks = [f"layer{s}.{i}" for s, n in enumerate(self.layers, start=1) for i in range(n)]
+        xin, ds_in = f16_empty(B * H * W, 64, dev), f16_empty(B * (H // 2) * (W // 2), 64, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mq_stem_conv3x3_f16(x.data_ptr(), B, H, W, self.conv1_wt16.data_ptr(), self.conv1_ps.data_ptr(),
+                                               self.conv1_pb.data_ptr(), self.prelu16.data_ptr(), self._v(blocks[0] + ".pre_scale").data_ptr(),
+                                               self._v(blocks[0] + ".pre_shift").data_ptr(), xin.data_ptr(), ds_in.data_ptr(), _stream(x)),
+                       "mq_stem_conv3x3_f16")
+        y = None
+        for bi, p in enumerate(blocks):
+            nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
+            o1, _, _ = self._conv3x3_f16(p + ".conv1", xin, B, H, W, slope=self._b(p + ".prelu16"))
+            if (p + ".downsample.0") in self._convs:
+                # the first block reads the stem's activation at even coordinates (stride 1 on D); later stages stride over y
+                src, h, w, stride = (ds_in, H // 2, W // 2, 1) if ds_in is not None else (y, H, W, 2)
+                name, c = p + ".downsample.0", self._convs[p + ".downsample.0"]
+                identity = f16_empty(B * ((h - 1) // stride + 1) * ((w - 1) // stride + 1), c.cout, dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.mq_conv1x1_f16(src.data_ptr(), B, h, w, c.cin, stride, self._b(name + ".w16").data_ptr(), c.cout,
+                                                  self._b(name + ".ps").data_ptr(), self._b(name + ".pb").data_ptr(), identity.data_ptr(),
+                                                  _stream(x)), "mq_conv1x1_f16")
+                ds_in = None
+            else:
+                identity = y
+            (y, xin), H, W = self._conv3x3_f16(p + ".conv2", o1, B, H, W, residual=identity,
+                                               scale=self._v(nxt + ".pre_scale") if nxt else None,
+                                               shift=self._v(nxt + ".pre_shift") if nxt else None)
+        A = SplitAct.empty(B, H * W * 512, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mq_head_prep_f16(y.data_ptr(), B, H * W, 512, self._v("head.pre_scale").data_ptr(),
+                                            self._v("head.pre_shift").data_ptr(), A.hi.data_ptr(), A.lo.data_ptr(), _stream(x)),
+                       "mq_head_prep_f16")
+        return self._fc(A, x)

@@ -19,6 +19,9 @@
 //                         epilogue.  The explicit path (im2col + GEMM: ~150 MB of patches per face, as long as the 12.6 GFLOP of matrix
 //                         work) remains for the strided 1 x 1 downsamples and the head, and as the check of the implicit one.
 //   stem_conv_kernel      the 3 -> 64 stem (K = 27) as a direct fp32 convolution fused with PReLU.
+// The opt-in fp16 trunk (mq_*_f16: the reference's own fp16 autocast precision) runs the same 3 x 3 kernels with F16 = true -- one fp16
+// tensor per activation, one v_mfma_f32_32x32x16_f16 per 16 k, autocast's rounding points in the epilogues (no BatchNorm folded) --
+// plus stem_conv_f16_kernel, conv1x1_f16_kernel (the strided downsample) and head_prep_f16_kernel (bn2 -> the head GEMM's pair).
 // Neither OpenCV, scikit-image nor arcface_torch is vendored by the reference or installable here: this path is "parity unpinned"
 // (oracle/arcface.py restates the published algorithms).
 #include <hip/hip_runtime.h>
@@ -32,6 +35,10 @@
 namespace {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+
+// r(): round to fp16 and back -- v_cvt_f16_f32, round to nearest even, overflow to +-inf (Tensor.half())
+__device__ __forceinline__ float rh(float x) { return (float)(_Float16)x; }
 
 // element (row, col) of a pair [M, K] (encoder.hip, PAIR LAYOUT)
 __device__ __forceinline__ size_t pair_index(size_t row, int col, int K) {
@@ -151,12 +158,43 @@ struct ConvArgs {
     const void* zeros;              // >= 16 bytes of zeros: the padded border
     int H, W, C, N, stride, Ho, Wo, M, ntm, ntn;
     int cmajor;  // K steps in (channel block, tap) order instead of (tap, channel block): see mq_conv3x3_pair_f32
+    // fp16 mode (mq_conv3x3_f16): Xh / Wh / Ph are fp16, Xl / Wl / Pl unused; the BatchNorm behind the convolution is NOT folded
+    const float *pscale, *pshift;   // r(r(acc) * pscale + pshift)
+    const unsigned short* R16;      // EP_RESIDUAL_AFFINE: fp16 shortcut, PAIR LAYOUT over [M, N]
+    unsigned short* Y16;            // EP_RESIDUAL_AFFINE: fp16 r(. + R16), PAIR LAYOUT over [M, N]
 };
 
-template <int RG, int WN, int EP>
+// fp16 epilogue after the transposition: columns gn ... gn + 7 of output row gm, t = r(bn(r(acc))) (PReLU applied for EP_PRELU_PAIR)
+//   EP_PRELU_PAIR       P = t
+//   EP_RESIDUAL_AFFINE  Y16 = r(t + R16);  P = r(Y16 * scale + shift) when scale is given
+template <int EP>
+__device__ __forceinline__ void store_f16(const ConvArgs& a, int gm, int gn, float4 u, float4 v) {
+    float t[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+    const size_t pt = pair_index((size_t)gm, gn, a.N);
+    if (EP == EP_RESIDUAL_AFFINE) {
+        const f16x8_t r = *reinterpret_cast<const f16x8_t*>(a.R16 + pt);
+        f16x8_t y;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            y[e] = (_Float16)(t[e] + (float)r[e]);
+            t[e] = (float)y[e];
+        }
+        *reinterpret_cast<f16x8_t*>(a.Y16 + pt) = y;
+        if (!a.scale) return;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t[e] = __builtin_fmaf(t[e], a.scale[gn + e], a.shift[gn + e]);
+    }
+    f16x8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (_Float16)t[e];
+    *reinterpret_cast<f16x8_t*>(a.Ph + pt) = o;
+}
+
+template <int RG, int WN, int EP, bool F16 = false>
 __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
     constexpr int CG = 16 / RG, MT = 64 * RG, NT = WN * CG, NF = WN / 32, AP = MT / 256;
-    constexpr int A_BYTES = MT * 64, W_BYTES = NT * 64, STAGE = 2 * A_BYTES + 2 * W_BYTES;
+    constexpr int NARR = F16 ? 1 : 2;  // arrays per operand: the (hi, lo) pair, or one fp16 tensor
+    constexpr int A_BYTES = MT * 64, W_BYTES = NT * 64, STAGE = NARR * A_BYTES + NARR * W_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -217,13 +255,13 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
             const size_t off = ((size_t)(p >> 8) * (size_t)CB + (size_t)cb) * 16384 + (size_t)((p & 255u) * 64u + chunk_bytes[j]);
             const unsigned dst = so + (unsigned)(16 * (w + 16 * j) * 64);
             dma16v(ok ? xh + off : zp, dst);
-            dma16v(ok ? xl + off : zp, dst + A_BYTES);
+            if constexpr (!F16) dma16v(ok ? xl + off : zp, dst + A_BYTES);
         }
         if (w < NT / 16) {
-            const unsigned dst = so + 2 * A_BYTES + (unsigned)(16 * w * 64);
+            const unsigned dst = so + NARR * A_BYTES + (unsigned)(16 * w * 64);
             const size_t kw_ = (size_t)__builtin_amdgcn_readfirstlane(tap * CB + cb) * 16384;  // the weights' K order is (tap, channel) either way
             dma16s(wh0 + kw_, w_voff, dst);
-            dma16s(wl0 + kw_, w_voff, dst + W_BYTES);
+            if constexpr (!F16) dma16s(wl0 + kw_, w_voff, dst + W_BYTES);
         }
         if (a.cmajor) { if (++tap == 9) { tap = 0; ++cb; } }
         else if (++cb == CB) { cb = 0; ++tap; }
@@ -232,7 +270,7 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
     const int i = lane & 31, kg = lane >> 5;
     const int sww = (i >> 2) & 3;
     const char* ard = smem + (64 * wr + i) * 64;                   // Ah rows of this wave; Al at + A_BYTES
-    const char* wrd = smem + 2 * A_BYTES + (WN * wc + i) * 64;     // Wh rows of this wave; Wl at + W_BYTES
+    const char* wrd = smem + NARR * A_BYTES + (WN * wc + i) * 64;  // Wh rows of this wave; Wl at + W_BYTES
     f32x16 acc[2][NF];
 #pragma unroll
     for (int x = 0; x < 2; ++x)
@@ -248,6 +286,24 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
         if (kb + 1 < nk) issue(kb + 1, stage ^ 1);
         const char* as = ard + stage * STAGE;
         const char* ws = wrd + stage * STAGE;
+        if constexpr (F16) {
+            // one v_mfma_f32_32x32x16_f16 per accumulator and 16 k: (2 + NF) fragment reads for 2 NF products
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int o = ((2 * m + kg) ^ sww) * 16;
+                f16x8_t ah[2], wh[NF];
+#pragma unroll
+                for (int x = 0; x < 2; ++x) ah[x] = *reinterpret_cast<const f16x8_t*>(as + x * 32 * 64 + o);
+#pragma unroll
+                for (int y = 0; y < NF; ++y) wh[y] = *reinterpret_cast<const f16x8_t*>(ws + y * 32 * 64 + o);
+#pragma unroll
+                for (int x = 0; x < 2; ++x)
+#pragma unroll
+                    for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[x], wh[y], acc[x][y], 0, 0, 0);
+            }
+            stage ^= 1;
+            continue;
+        }
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const int o = ((2 * m + kg) ^ sww) * 16;
@@ -289,13 +345,20 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
 #pragma unroll
         for (int y = 0; y < NF; ++y) {
             const int col = n0 + WN * wc + 32 * y + i;
-            const float bs = a.bias[col];
+            const float bs = F16 ? a.pshift[col] : a.bias[col];
+            const float ps = F16 ? a.pscale[col] : 0.f;
             const float sl = EP == EP_PRELU_PAIR ? a.slope[col] : 0.f;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kg;
-                float v = acc[x][y][reg] + bs;
-                if (EP == EP_PRELU_PAIR) v = v >= 0.f ? v : v * sl;
+                float v;
+                if constexpr (F16) {
+                    v = rh(__builtin_fmaf(rh(acc[x][y][reg]), ps, bs));
+                    if (EP == EP_PRELU_PAIR) v = rh(v >= 0.f ? v : v * sl);
+                } else {
+                    v = acc[x][y][reg] + bs;
+                    if (EP == EP_PRELU_PAIR) v = v >= 0.f ? v : v * sl;
+                }
                 Ot[row * 32 + ((((i >> 3) ^ (row & 3)) << 3) | (i & 7))] = v;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -305,7 +368,9 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
                 const float* src = Ot + row * 32 + ((g ^ (row & 3)) << 3);
                 float4 u = *reinterpret_cast<const float4*>(src), v = *reinterpret_cast<const float4*>(src + 4);
                 const int gm = m0 + 64 * wr + 32 * x + row, gn = n0 + WN * wc + 32 * y + 8 * g;
-                if (gm < a.M) {
+                if (F16 && gm < a.M) {
+                    store_f16<EP>(a, gm, gn, u, v);
+                } else if (gm < a.M) {
                     bool pair_out = true;
                     if (EP == EP_RESIDUAL_AFFINE) {
                         const size_t at = (size_t)gm * a.N + gn;
@@ -359,9 +424,13 @@ constexpr int PT_MT = 256, PT_NT = 64, PT_PR = 512, PT_WS = 4;
 constexpr int PT_PATCH = PT_PR * 128;            // one patch buffer: hi rows then lo rows, 64 bytes each
 constexpr int PT_WSTAGE = PT_NT * 128;           // one weight stage: hi rows then lo rows
 constexpr int PT_LDS = 2 * PT_PATCH + PT_WS * PT_WSTAGE;   // 160 KiB
+// fp16 mode: one array per operand -- half the patch and weight bytes (80 KiB), four weight waves instead of eight
+constexpr int PT_LDS16 = 2 * PT_PATCH / 2 + PT_WS * PT_WSTAGE / 2;
 
-template <int EP>
+template <int EP, bool F16 = false>
 __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
+    constexpr int PATCH = F16 ? PT_PATCH / 2 : PT_PATCH, WSTAGE = F16 ? PT_WSTAGE / 2 : PT_WSTAGE;
+    constexpr int WWAVES = F16 ? 4 : 8;  // waves that load weights: one 1-KiB piece each per tap
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -404,17 +473,17 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
             const unsigned pu = (unsigned)p;
             const size_t off = ((size_t)(pu >> 8) * (size_t)CB + (size_t)cb) * 16384 +
                                (size_t)((pu & 255u) * 64u + (((unsigned)(lane & 3) ^ (unsigned)((rho >> 2) & 3)) * 16u));
-            const unsigned dst = lds0 + (unsigned)(buf * PT_PATCH + 16 * (w + 16 * j) * 64);
+            const unsigned dst = lds0 + (unsigned)(buf * PATCH + 16 * (w + 16 * j) * 64);
             dma16v(ok ? xh + off : zp, dst);
-            dma16v(ok ? xl + off : zp, dst + PT_PR * 64);
+            if constexpr (!F16) dma16v(ok ? xl + off : zp, dst + PT_PR * 64);
         }
     };
-    // weight piece of waves 0-7: array w >> 2 (hi, lo), rows 16 (w & 3) ... of the tap's 64-row stage
+    // weight piece of waves 0-7: array w >> 2 (hi, lo), rows 16 (w & 3) ... of the tap's 64-row stage (fp16: waves 0-3, one array)
     const int wrow = 16 * (w & 3) + (lane >> 2);
     const unsigned w_voff = (unsigned)(((n0 & 255) + wrow) * 64) + (((unsigned)(lane & 3) ^ (unsigned)((wrow >> 2) & 3)) * 16u);
     const char* wbase = reinterpret_cast<const char*>((w >> 2) ? a.Wl : a.Wh) + (size_t)(n0 >> 8) * (size_t)nk * 16384;
     auto issue_w = [&](int step) __attribute__((always_inline)) {  // step = cb * 9 + tap; weights' K order is (tap, channel block)
-        const unsigned dst = lds0 + (unsigned)(2 * PT_PATCH + (step & (PT_WS - 1)) * PT_WSTAGE + (w >> 2) * (PT_NT * 64) + (w & 3) * 1024);
+        const unsigned dst = lds0 + (unsigned)(2 * PATCH + (step & (PT_WS - 1)) * WSTAGE + (w >> 2) * (PT_NT * 64) + (w & 3) * 1024);
         if (step < nk) {
             const int cb = step / 9, tap = step - cb * 9;
             dma16s(wbase + (size_t)__builtin_amdgcn_readfirstlane(tap * CB + cb) * 16384, w_voff, dst);
@@ -425,32 +494,48 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
 
     f32x16 acc = {0};
     issue_patch(0, true, 0);
-    if (w < 8) { issue_w(0); issue_w(1); issue_w(2); }
+    if (w < WWAVES) { issue_w(0); issue_w(1); issue_w(2); }
     const int sww = (i >> 2) & 3;
-    const char* wrd0 = smem + 2 * PT_PATCH + (32 * wc + i) * 64;
+    const char* wrd0 = smem + 2 * PATCH + (32 * wc + i) * 64;
     for (int cb = 0; cb < CB; ++cb) {
-        const char* pbuf = smem + (cb & 1) * PT_PATCH;
+        const char* pbuf = smem + (cb & 1) * PATCH;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int step = cb * 9 + tap;
             // in-order counter: everything up to this step's weight stage (and, at tap 0, this block's patch) has landed when at
             // most the younger requests are outstanding: two weight pieces, plus the next patch's four between taps 0 and 3
-            if (w < 8) {
-                if (tap == 1 || tap == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            // (fp16: two patch pieces, so 4 instead of 6)
+            if (w < WWAVES) {
+                if (tap == 1 || tap == 2) {
+                    if constexpr (F16) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+                } else {
+                    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                }
             } else if (tap == 0) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             if (tap == 0) issue_patch(cb + 1, cb + 1 < CB, (cb + 1) & 1);
-            if (w < 8) issue_w(step + 3);
+            if (w < WWAVES) issue_w(step + 3);
             const int off = (tap / 3) * W + (tap % 3);
             const int rho = 32 * wr + i + off;
             const int key = (rho >> 2) & 3;
             const char* ap = pbuf + rho * 64;
-            const char* wp = wrd0 + (step & (PT_WS - 1)) * PT_WSTAGE;
+            const char* wp = wrd0 + (step & (PT_WS - 1)) * WSTAGE;
             const bool ok = (mask >> tap) & 1u;
+            if constexpr (F16) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const int c = 2 * m + kg;
+                    f16x8_t ah = *reinterpret_cast<const f16x8_t*>(ap + ((c ^ key) << 4));
+                    const f16x8_t wh = *reinterpret_cast<const f16x8_t*>(wp + ((c ^ sww) << 4));
+                    if (!ok) ah = __builtin_bit_cast(f16x8_t, make_uint4(0u, 0u, 0u, 0u));
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc, 0, 0, 0);
+                }
+                continue;
+            }
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const int c = 2 * m + kg;
@@ -476,13 +561,20 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
     float* Ot = reinterpret_cast<float*>(smem) + w * 1024;
     {
         const int col = n0 + 32 * wc + i;
-        const float bs = a.bias[col];
+        const float bs = F16 ? a.pshift[col] : a.bias[col];
+        const float ps = F16 ? a.pscale[col] : 0.f;
         const float sl = EP == EP_PRELU_PAIR ? a.slope[col] : 0.f;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int row = (reg & 3) + 8 * (reg >> 2) + 4 * kg;
-            float v = acc[reg] + bs;
-            if (EP == EP_PRELU_PAIR) v = v >= 0.f ? v : v * sl;
+            float v;
+            if constexpr (F16) {
+                v = rh(__builtin_fmaf(rh(acc[reg]), ps, bs));
+                if (EP == EP_PRELU_PAIR) v = rh(v >= 0.f ? v : v * sl);
+            } else {
+                v = acc[reg] + bs;
+                if (EP == EP_PRELU_PAIR) v = v >= 0.f ? v : v * sl;
+            }
             Ot[row * 32 + ((((i >> 3) ^ (row & 3)) << 3) | (i & 7))] = v;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -492,7 +584,9 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
             const float* src = Ot + row * 32 + ((g ^ (row & 3)) << 3);
             float4 u = *reinterpret_cast<const float4*>(src), v = *reinterpret_cast<const float4*>(src + 4);
             const int gm = m0 + 32 * wr + row, gn = n0 + 32 * wc + 8 * g;
-            if (gm < a.M) {
+            if (F16 && gm < a.M) {
+                store_f16<EP>(a, gm, gn, u, v);
+            } else if (gm < a.M) {
                 bool pair_out = true;
                 if (EP == EP_RESIDUAL_AFFINE) {
                     const size_t at = (size_t)gm * a.N + gn;
@@ -535,39 +629,40 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
         if (_e != hipSuccess) return MQ_EHIP;           \
     } while (0)
 
-template <int RG, int WN, int EP>
+template <int RG, int WN, int EP, bool F16 = false>
 int launch_conv3x3(ConvArgs a, hipStream_t st) {
-    constexpr int CG = 16 / RG, MT = 64 * RG, NT = WN * CG;
-    constexpr int LDS = 2 * (2 * MT * 64 + 2 * NT * 64);
-    static_assert(LDS >= 16 * 4096, "the epilogue's scratch: 4 KiB per wave");
+    constexpr int CG = 16 / RG, MT = 64 * RG, NT = WN * CG, NARR = F16 ? 1 : 2;
+    constexpr int STAGES = 2 * (NARR * MT * 64 + NARR * NT * 64);
+    constexpr int LDS = STAGES > 16 * 4096 ? STAGES : 16 * 4096;  // the epilogue's scratch: 4 KiB per wave
     a.ntm = (a.M + MT - 1) / MT;
     a.ntn = a.N / NT;
     const int ntiles = ((a.ntm + 7) >> 3) * 8 * a.ntn;
-    MQ_DYNAMIC_LDS_WITH(CONV_HIP, LDS, conv3x3_x3s_kernel<RG, WN, EP>);
-    hipLaunchKernelGGL((conv3x3_x3s_kernel<RG, WN, EP>), dim3((unsigned)ntiles), dim3(1024), LDS, st, a);
+    MQ_DYNAMIC_LDS_WITH(CONV_HIP, LDS, conv3x3_x3s_kernel<RG, WN, EP, F16>);
+    hipLaunchKernelGGL((conv3x3_x3s_kernel<RG, WN, EP, F16>), dim3((unsigned)ntiles), dim3(1024), LDS, st, a);
     return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
 }
 
-template <int EP>
+template <int EP, bool F16 = false>
 int launch_conv3x3_patch(ConvArgs a, hipStream_t st) {
+    constexpr int LDS = F16 ? PT_LDS16 : PT_LDS;
     a.ntm = (a.M + PT_MT - 1) / PT_MT;
     a.ntn = a.N / PT_NT;
     const int ntiles = ((a.ntm + 7) >> 3) * 8 * a.ntn;
-    MQ_DYNAMIC_LDS_WITH(CONV_HIP, PT_LDS, conv3x3_patch_kernel<EP>);
-    hipLaunchKernelGGL((conv3x3_patch_kernel<EP>), dim3((unsigned)ntiles), dim3(1024), PT_LDS, st, a);
+    MQ_DYNAMIC_LDS_WITH(CONV_HIP, LDS, conv3x3_patch_kernel<EP, F16>);
+    hipLaunchKernelGGL((conv3x3_patch_kernel<EP, F16>), dim3((unsigned)ntiles), dim3(1024), LDS, st, a);
     return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
 }
 
-template <int EP>
+template <int EP, bool F16 = false>
 int launch_conv3x3_variant(const ConvArgs& a, int variant, hipStream_t st) {
     switch (variant) {
         case MQ_CONV_TILE_PATCH_256x64:
             // the patch is linear in the pixel index: stride 1, and 256 + 2 W + 2 rows must fit the 512-row buffer
-            return (a.stride != 1 || a.N % 64 || 2 * a.W + 2 > PT_PR - PT_MT || !a.cmajor) ? MQ_EINVAL : launch_conv3x3_patch<EP>(a, st);
-        case MQ_CONV_TILE_256x256: return a.N % 256 ? MQ_EINVAL : launch_conv3x3<4, 64, EP>(a, st);
-        case MQ_CONV_TILE_512x128: return a.N % 128 ? MQ_EINVAL : launch_conv3x3<8, 64, EP>(a, st);
-        case MQ_CONV_TILE_256x128: return a.N % 128 ? MQ_EINVAL : launch_conv3x3<4, 32, EP>(a, st);
-        case MQ_CONV_TILE_512x64: return a.N % 64 ? MQ_EINVAL : launch_conv3x3<8, 32, EP>(a, st);
+            return (a.stride != 1 || a.N % 64 || 2 * a.W + 2 > PT_PR - PT_MT || !a.cmajor) ? MQ_EINVAL : launch_conv3x3_patch<EP, F16>(a, st);
+        case MQ_CONV_TILE_256x256: return a.N % 256 ? MQ_EINVAL : launch_conv3x3<4, 64, EP, F16>(a, st);
+        case MQ_CONV_TILE_512x128: return a.N % 128 ? MQ_EINVAL : launch_conv3x3<8, 64, EP, F16>(a, st);
+        case MQ_CONV_TILE_256x128: return a.N % 128 ? MQ_EINVAL : launch_conv3x3<4, 32, EP, F16>(a, st);
+        case MQ_CONV_TILE_512x64: return a.N % 64 ? MQ_EINVAL : launch_conv3x3<8, 32, EP, F16>(a, st);
     }
     return MQ_EINVAL;
 }
@@ -579,6 +674,40 @@ int launch_conv3x3_variant(const ConvArgs& a, int variant, hipStream_t st) {
 //   D  = split(prelu(conv + bias)) at even (h, w)    the A operand of the first block's strided 1 x 1 downsample, [B H/2 W/2, 64]
 // A thread = 4 horizontally adjacent pixels x 8 output channels (32 accumulators; the 27 x 64 weights sit in LDS, one 32-byte read
 // per tap serves 4 x 8 multiply-adds); fp32 fused multiply-adds in (kh, kw, c) order: fp32-exact products, one rounding per term.
+// acc[p][j] += the 27 terms of pixel (h, w0 + p), channel ch0 + j; F16: the pixels rounded to fp16 first (the weights in ws already are)
+template <bool F16>
+__device__ __forceinline__ void stem_taps(const float* __restrict__ xb, const float* ws, int h, int w0, int H, int W, int ch0,
+                                          float (&acc)[4][8]) {
+    const size_t plane = (size_t)H * W;
+#pragma unroll 1
+    for (int kh = 0; kh < 3; ++kh) {
+        const int ih = h + kh - 1;
+        const bool rok = ih >= 0 && ih < H;
+        float in[3][6];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const int iw = w0 + j - 1;
+                in[c][j] = (rok && iw >= 0 && iw < W) ? xb[(size_t)c * plane + (size_t)ih * W + iw] : 0.f;
+                if (F16) in[c][j] = rh(in[c][j]);
+            }
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float* wp = ws + ((kh * 3 + kw) * 3 + c) * 64 + ch0;
+                const float4 u = *reinterpret_cast<const float4*>(wp), v = *reinterpret_cast<const float4*>(wp + 4);
+                const float wv[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[p][j] = __builtin_fmaf(in[c][p + kw], wv[j], acc[p][j]);
+                asm volatile("" ::: "memory");  // one tap's weights live at a time (hoisted, the 27 reads need 216 registers)
+            }
+    }
+}
+
 __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const float* __restrict__ x, const float* __restrict__ wt, const float* __restrict__ bias,
                                                         const float* __restrict__ slope, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, unsigned short* __restrict__ Ph,
@@ -602,34 +731,7 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const float* __restri
             acc[p][4] = b1.x; acc[p][5] = b1.y; acc[p][6] = b1.z; acc[p][7] = b1.w;
         }
     }
-    const size_t plane = (size_t)H * W;
-    const float* xb = x + (size_t)b * 3 * plane;
-#pragma unroll 1
-    for (int kh = 0; kh < 3; ++kh) {
-        const int ih = h + kh - 1;
-        const bool rok = ih >= 0 && ih < H;
-        float in[3][6];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int iw = w0 + j - 1;
-                in[c][j] = (rok && iw >= 0 && iw < W) ? xb[(size_t)c * plane + (size_t)ih * W + iw] : 0.f;
-            }
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* wp = ws + ((kh * 3 + kw) * 3 + c) * 64 + ch0;
-                const float4 u = *reinterpret_cast<const float4*>(wp), v = *reinterpret_cast<const float4*>(wp + 4);
-                const float wv[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[p][j] = __builtin_fmaf(in[c][p + kw], wv[j], acc[p][j]);
-                asm volatile("" ::: "memory");  // one tap's weights live at a time (hoisted, the 27 reads need 216 registers)
-            }
-    }
+    stem_taps<false>(x + (size_t)b * 3 * H * W, ws, h, w0, H, W, ch0, acc);
     float sl[8], sc[8], sh[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sl[j] = slope[ch0 + j]; sc[j] = scale[ch0 + j]; sh[j] = shift[ch0 + j]; }
@@ -660,6 +762,111 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const float* __restri
             *reinterpret_cast<bf16x8_t*>(Dl + ad) = dl8;
         }
     }
+}
+
+// The stem at the reference's autocast precision: the pixels and the UNFOLDED weights (wt, already fp16 values) in fp16, fp32
+// accumulation from zero (the convolution has no bias), then v = r(prelu(r(bn1(r(acc))), slope)) (slope: fp16 values) and
+//   P = r(v * scale + shift)   fp16, PAIR LAYOUT over [B H W, 64]: the first block's conv1 input (its bn1 applied)
+//   D = v at even (h, w)       fp16, PAIR LAYOUT over [B H/2 W/2, 64]: the operand of the first block's strided 1 x 1 downsample
+__global__ __launch_bounds__(256, 4) void stem_conv_f16_kernel(const float* __restrict__ x, const float* __restrict__ wt,
+                                                            const float* __restrict__ pscale, const float* __restrict__ pshift,
+                                                            const float* __restrict__ slope, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, unsigned short* __restrict__ P,
+                                                            unsigned short* __restrict__ D, int B, int H, int W) {
+    __shared__ __attribute__((aligned(16))) float ws[27 * 64];
+    for (int e = threadIdx.x; e < 27 * 64; e += 256) ws[e] = wt[e];
+    __syncthreads();
+    const int cg = threadIdx.x & 7, ch0 = cg * 8;
+    const unsigned qpr = (unsigned)W >> 2, qpi = qpr * (unsigned)H;
+    const unsigned q = blockIdx.x * 32u + (threadIdx.x >> 3);
+    if (q >= (unsigned)B * qpi) return;
+    const unsigned b = q / qpi, rem = q - b * qpi;
+    const int h = (int)(rem / qpr), w0 = (int)(rem - (unsigned)h * qpr) * 4;
+    float acc[4][8];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[p][j] = 0.f;
+    stem_taps<true>(x + (size_t)b * 3 * H * W, ws, h, w0, H, W, ch0, acc);
+    float ps[8], pb[8], sl[8], sc[8], sh[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        ps[j] = pscale[ch0 + j]; pb[j] = pshift[ch0 + j]; sl[j] = slope[ch0 + j]; sc[j] = scale[ch0 + j]; sh[j] = shift[ch0 + j];
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        f16x8_t p8, d8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float v = rh(__builtin_fmaf(rh(acc[p][j]), ps[j], pb[j]));
+            v = rh(v >= 0.f ? v : v * sl[j]);
+            d8[j] = (_Float16)v;
+            p8[j] = (_Float16)__builtin_fmaf(v, sc[j], sh[j]);
+        }
+        const int wq = w0 + p;
+        const size_t m = ((size_t)b * H + h) * W + wq;
+        *reinterpret_cast<f16x8_t*>(P + pair_index(m, ch0, 64)) = p8;
+        if (D && !(h & 1) && !(wq & 1)) {
+            const size_t md = ((size_t)b * (H >> 1) + (h >> 1)) * (W >> 1) + (wq >> 1);
+            *reinterpret_cast<f16x8_t*>(D + pair_index(md, ch0, 64)) = d8;
+        }
+    }
+}
+
+// ---- fp16 1 x 1 convolution, stride 1 or 2, no padding (IResNet's downsample): Y = r(r(conv) * pscale + pshift), fp16 PAIR LAYOUT over
+// [B Ho Wo, N].  A workgroup = 64 output pixels x 64 channels, four waves of 32 x 32; the operands go straight from global memory into
+// the fragment registers (K = C <= 256: 4 - 16 steps of one v_mfma_f32_32x32x16_f16): the A rows of a lane are one input pixel's 16
+// contiguous bytes in the activation's 64-byte rows, the weights are row-major [N, C] fp16.  ~1 % of the forward's products.
+__global__ __launch_bounds__(256) void conv1x1_f16_kernel(const unsigned short* __restrict__ X, int H, int W, int C, int stride, int Ho,
+                                                          int Wo, int M, const unsigned short* __restrict__ Wt, int N,
+                                                          const float* __restrict__ pscale, const float* __restrict__ pshift,
+                                                          unsigned short* __restrict__ Y) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 31, kg = lane >> 5;
+    const int m0 = (int)blockIdx.x * 64 + 32 * (w >> 1), n0 = (int)blockIdx.y * 64 + 32 * (w & 1);
+    // this lane's A row: output pixel m0 + i -> input pixel (b, ho * stride, wo * stride)
+    const int m = m0 + i < M ? m0 + i : M - 1;
+    const int hw = Ho * Wo, bi = m / hw, pix = m - bi * hw, ho = pix / Wo, wo = pix - ho * Wo;
+    const size_t p = ((size_t)bi * H + (size_t)ho * stride) * W + (size_t)wo * stride;
+    const unsigned short* wrow = Wt + (size_t)(n0 + i) * C;
+    f32x16 acc = {0};
+    for (int k = 0; k < C; k += 16) {
+        const f16x8_t av = *reinterpret_cast<const f16x8_t*>(X + pair_index(p, k + 8 * kg, C));
+        const f16x8_t bv = *reinterpret_cast<const f16x8_t*>(wrow + k + 8 * kg);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc, 0, 0, 0);
+    }
+    const int col = n0 + i;
+    const float ps = pscale[col], pb = pshift[col];
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int row = m0 + (reg & 3) + 8 * (reg >> 2) + 4 * kg;
+        if (row < M) Y[pair_index((size_t)row, col, N)] = __builtin_bit_cast(unsigned short, (_Float16)__builtin_fmaf(rh(acc[reg]), ps, pb));
+    }
+}
+
+// ---- the head's operand from the fp16 trunk: A[b, (h W + w) C + c] = split(r(t[b, h, w, c] * scale[c] + shift[c])) -- bn2, flatten in
+// NHWC order, .float() -- in the split pair (PAIR LAYOUT over [B, HW C]) of mq_gemm_nt_bf16x3s_splitk_f32.  An fp16 value is exactly
+// hi + lo in bf16 (11 significant bits = 8 + 3): the head's GEMM sees the fp32 value of the reference's fc(x.float()).  One thread = 8
+// channels of one pixel.
+__global__ __launch_bounds__(256) void head_prep_f16_kernel(const unsigned short* __restrict__ X, int B, int HW, int C,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            unsigned short* __restrict__ Ah, unsigned short* __restrict__ Al) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, per = (size_t)C >> 3;
+    if (e >= (size_t)B * HW * per) return;
+    const size_t row = e / per;                     // b * HW + pixel
+    const int c0 = (int)(e - row * per) * 8;
+    const int b = (int)(row / (size_t)HW), pix = (int)(row - (size_t)b * HW);
+    const f16x8_t x8 = *reinterpret_cast<const f16x8_t*>(X + pair_index(row, c0, C));
+    bf16x8_t h8, l8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float v = rh(__builtin_fmaf((float)x8[j], scale[c0 + j], shift[c0 + j]));
+        const __bf16 hb = (__bf16)v;
+        h8[j] = hb;
+        l8[j] = (__bf16)(__builtin_isinf(v) ? 0.f : v - (float)hb);  // +-inf: hi carries it (inf - inf would be a NaN)
+    }
+    const size_t at = pair_index((size_t)b, pix * C + c0, HW * C);
+    *reinterpret_cast<bf16x8_t*>(Ah + at) = h8;
+    *reinterpret_cast<bf16x8_t*>(Al + at) = l8;
 }
 
 // ---- cv2.warpAffine (INTER_LINEAR, BORDER_CONSTANT 0), as published in OpenCV's imgwarp.cpp ----
@@ -805,6 +1012,78 @@ int mq_stem_conv3x3_f32(const float* x_dev, int B, int H, int W, const float* wt
     hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)((quads + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, wt_dev, bias_dev,
                        prelu_slope_dev, scale_dev, shift_dev, (unsigned short*)Ph_dev, (unsigned short*)Pl_dev, (unsigned short*)Dh_dev,
                        (unsigned short*)Dl_dev, B, H, W);
+    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+}
+
+int mq_conv3x3_f16(const uint16_t* X_dev, int B, int H, int W, int C, int stride, const uint16_t* Wt_dev, int N, const float* post_scale_dev,
+                   const float* post_shift_dev, const float* prelu_slope_dev, const uint16_t* residual_dev, const float* scale_dev,
+                   const float* shift_dev, uint16_t* Y_dev, uint16_t* P_dev, const void* zeros_dev, int tile, void* stream) {
+    if (B == 0) return MQ_OK;
+    if (!X_dev || !Wt_dev || !post_scale_dev || !post_shift_dev || !zeros_dev || B < 0 || H <= 0 || W <= 0) return MQ_EINVAL;
+    if (C <= 0 || C % 32 || N <= 0 || N % 64 || (stride != 1 && stride != 2)) return MQ_EINVAL;
+    const bool prelu = prelu_slope_dev != nullptr;
+    if (prelu && (residual_dev || Y_dev || scale_dev || shift_dev || !P_dev)) return MQ_EINVAL;  // EP_PRELU_PAIR
+    if (!prelu && (!residual_dev || !Y_dev)) return MQ_EINVAL;                                   // EP_RESIDUAL_AFFINE
+    if ((scale_dev == nullptr) != (shift_dev == nullptr)) return MQ_EINVAL;
+    if (!prelu && scale_dev && !P_dev) return MQ_EINVAL;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const size_t M = (size_t)B * Ho * Wo, P = (size_t)B * H * W;
+    if (M >= 0x7FFFFFFFull || P >= 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
+    ConvArgs a = {};
+    a.Xh = X_dev; a.Wh = Wt_dev; a.slope = prelu_slope_dev; a.scale = scale_dev; a.shift = shift_dev; a.Ph = P_dev; a.zeros = zeros_dev;
+    a.pscale = post_scale_dev; a.pshift = post_shift_dev; a.R16 = residual_dev; a.Y16 = Y_dev;
+    a.H = H; a.W = W; a.C = C; a.N = N; a.stride = stride; a.Ho = Ho; a.Wo = Wo; a.M = (int)M;
+    a.cmajor = (tile & MQ_CONV_K_CHANNEL_MAJOR) ? 1 : 0;
+    tile &= ~MQ_CONV_K_CHANNEL_MAJOR;
+    if (tile == MQ_CONV_TILE_AUTO) {
+        // the 64-channel stage reads one LDS-resident patch per channel block; wider stages: the widest tile the channel count fills
+        // while it still gives every CU a workgroup
+        if (N == 64 && stride == 1 && a.cmajor && 2 * W + 2 <= PT_PR - PT_MT) tile = MQ_CONV_TILE_PATCH_256x64;
+        else if (N % 256 == 0 && ((M + 255) / 256) * (size_t)(N / 256) >= 192) tile = MQ_CONV_TILE_256x256;
+        else if (N % 128 == 0) tile = ((M + 511) / 512) * (size_t)(N / 128) >= 192 ? MQ_CONV_TILE_512x128 : MQ_CONV_TILE_256x128;
+        else tile = MQ_CONV_TILE_512x64;
+    }
+    return prelu ? launch_conv3x3_variant<EP_PRELU_PAIR, true>(a, tile, (hipStream_t)stream)
+                 : launch_conv3x3_variant<EP_RESIDUAL_AFFINE, true>(a, tile, (hipStream_t)stream);
+}
+
+int mq_stem_conv3x3_f16(const float* x_dev, int B, int H, int W, const float* wt_dev, const float* post_scale_dev, const float* post_shift_dev,
+                        const float* prelu_slope_dev, const float* scale_dev, const float* shift_dev, uint16_t* P_dev, uint16_t* D_dev,
+                        void* stream) {
+    if (B == 0) return MQ_OK;
+    if (!x_dev || !wt_dev || !post_scale_dev || !post_shift_dev || !prelu_slope_dev || !scale_dev || !shift_dev || !P_dev) return MQ_EINVAL;
+    if (B < 0 || H <= 0 || W <= 0) return MQ_EINVAL;
+    if ((W & 3) || (D_dev && (H & 1))) return MQ_EUNSUPPORTED;
+    const size_t quads = (size_t)B * H * (W / 4);
+    if ((quads + 31) / 32 > 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
+    hipLaunchKernelGGL(stem_conv_f16_kernel, dim3((unsigned)((quads + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, wt_dev,
+                       post_scale_dev, post_shift_dev, prelu_slope_dev, scale_dev, shift_dev, (unsigned short*)P_dev, (unsigned short*)D_dev,
+                       B, H, W);
+    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+}
+
+int mq_conv1x1_f16(const uint16_t* X_dev, int B, int H, int W, int C, int stride, const uint16_t* Wt_dev, int N, const float* post_scale_dev,
+                   const float* post_shift_dev, uint16_t* Y_dev, void* stream) {
+    if (B == 0) return MQ_OK;
+    if (!X_dev || !Wt_dev || !post_scale_dev || !post_shift_dev || !Y_dev || B < 0 || H <= 0 || W <= 0) return MQ_EINVAL;
+    if (C <= 0 || C % 32 || N <= 0 || N % 64 || (stride != 1 && stride != 2)) return MQ_EINVAL;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const size_t M = (size_t)B * Ho * Wo, P = (size_t)B * H * W;
+    if (M >= 0x7FFFFFFFull || P >= 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
+    hipLaunchKernelGGL(conv1x1_f16_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(N / 64)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned short*)X_dev, H, W, C, stride, Ho, Wo, (int)M, (const unsigned short*)Wt_dev, N, post_scale_dev,
+                       post_shift_dev, (unsigned short*)Y_dev);
+    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+}
+
+int mq_head_prep_f16(const uint16_t* X_dev, int B, int HW, int C, const float* scale_dev, const float* shift_dev, uint16_t* Ah_dev,
+                     uint16_t* Al_dev, void* stream) {
+    if (B == 0) return MQ_OK;
+    if (!X_dev || !scale_dev || !shift_dev || !Ah_dev || !Al_dev || B < 0 || HW <= 0 || C <= 0 || C % 32) return MQ_EINVAL;
+    const size_t threads = (size_t)B * HW * (C / 8);
+    if ((size_t)HW * C >= 0x7FFFFFFFull || (threads + 255) / 256 > 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
+    hipLaunchKernelGGL(head_prep_f16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned short*)X_dev, B, HW, C, scale_dev, shift_dev, (unsigned short*)Ah_dev, (unsigned short*)Al_dev);
     return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
 }
 

@@ -5,7 +5,7 @@ Same names and call shapes as the reference for the hot-path surface:
 
 * ``SRC``, ``ARCFACE_PATH``, ``PRETRAINED_MODELS``            :29-40
 * ``similarity_transform(image, landmarks, src, tform)``        :44-52   (one face, on the host: PIL in, PIL out)
-* ``from_pretrained(model_name='r50', fp16=True, train=False)`` :55-61   -> :class:`viquae_amd.arcface.ArcFaceR50`
+* ``from_pretrained(model_name='r50', fp16=True, train=False, precision=None)`` :55-61   -> :class:`viquae_amd.arcface.ArcFaceR50`
 * ``get_pil_preprocessor()``                                    :64-70
 * ``compute_face_embedding(batch, model, preprocessor, tform, max_n_faces=1, image_key='image')``   :72-102
 * ``dataset_compute_face_embedding(dataset_path, map_kwargs, pretrained_kwargs, fn_kwargs)``        :105-112
@@ -14,7 +14,8 @@ What differs underneath: the reference aligns every face on the host (scikit-ima
 torchvision's ToTensor / Normalize), one at a time; here only the 2 x 3 matrices are estimated on the host (numpy, a few hundred
 flops per face) and ``compute_face_embedding`` cuts, scales and normalises ALL faces of a batch in one kernel
 (``mq_warp_affine_faces_f32``: OpenCV's fixed-point bilinear arithmetic + ToTensor + Normalize) from the decoded images packed in
-one device buffer, then runs :class:`ArcFaceR50`.  ``fp16`` is accepted and ignored: the HIP model is fp32-class throughout.
+one device buffer, then runs :class:`ArcFaceR50`.  By default the HIP model is fp32-class throughout; ``precision="fp16"`` (or
+``MQ_ARCFACE_PRECISION=fp16``) runs it at the reference's own fp16 autocast precision.
 
 Neither scikit-image, OpenCV nor arcface_torch is vendored by the reference or installable here: parity unpinned
 (oracle/arcface.py restates the published algorithms; tests/test_arcface_gpu.py)."""
@@ -148,15 +149,26 @@ def similarity_transform(image, landmarks, src, tform, image_size=IMAGE_SIZE):
     return Image.fromarray(face)
 
 
-def from_pretrained(model_name="r50", fp16=True, train=False):
-    """:55-61.  ``fp16`` (the reference's autocast switch) is accepted and ignored; ``train=True`` is not supported (inference)."""
-    from ..arcface import ArcFaceR50
+def from_pretrained(model_name="r50", fp16=True, train=False, precision=None):
+    """:55-61.  ``precision``: "fp32" (fp32-class, the default) or "fp16" (the trunk at the reference's fp16 autocast rounding
+    points, the head in fp32); None reads ``MQ_ARCFACE_PRECISION`` (default "fp32").  ``fp16`` is the reference's autocast switch:
+    it permits the fp16 precision (``precision="fp16"`` with ``fp16=False`` is a ValueError) but does not select it.  ``train=True``
+    is not supported (inference)."""
+    import os
+
+    from ..arcface import PRECISIONS, ArcFaceR50
+    if precision is None:
+        precision = os.environ.get("MQ_ARCFACE_PRECISION", "fp32")
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    if precision == "fp16" and not fp16:
+        raise ValueError("precision='fp16' needs fp16=True (the reference's autocast switch)")
     from ..utils import device
     if model_name not in PRETRAINED_MODELS:
         raise KeyError(model_name)
     if train:
         raise NotImplementedError("the HIP face encoder is inference-only")
-    return ArcFaceR50.from_pretrained(PRETRAINED_MODELS[model_name]).to(device=device)
+    return ArcFaceR50.from_pretrained(PRETRAINED_MODELS[model_name], precision=precision).to(device=device)
 
 
 def get_pil_preprocessor():
