@@ -512,21 +512,15 @@ def test_eca_with_the_shipped_max_length_text_plus_faces_plus_image():
                 face_inputs={"face": _cuda(face), "bbox": _cuda(bbox), "attention_mask": _cuda(fmask)},
                 image_inputs={"clip-RN50": {"input": _cuda(img), "attention_mask": torch.ones((B, 1), dtype=torch.long, device="cuda")}})
     calls = []
-    orig, orig_packed = E._pooled_by_groups, model.bert_model.packed_layers
-    E._pooled_by_groups = lambda *a, **k: (calls.append("groups"), orig(*a, **k))[1]
+    orig_packed = model.bert_model.packed_layers
     model.bert_model.packed_layers = lambda *a, **k: (calls.append("packed"), orig_packed(*a, **k))[1]
     try:
         fast = model(**args)["pooler_output"].cpu().numpy()           # the packed forward over the compacted joint sequences
-        os.environ["MQ_ENC_PACKED"] = "0"
-        groups = model(**args)["pooler_output"].cpu().numpy()         # length groups (the round-2 path)
     finally:
-        E._pooled_by_groups = orig
         del model.bert_model.packed_layers
-        os.environ.pop("MQ_ENC_PACKED", None)
-    assert calls == ["packed", "groups"], "the compaction paths did not run"
+    assert calls == ["packed"], "the compaction path did not run"
     dense = model(output_hidden_states=True, **args)["pooler_output"].cpu().numpy()
     assert np.abs(fast - want2).max() < TOL and np.abs(fast - dense).max() < 3e-5  # shortcuts read from 16-bit pairs (round 4): 2^-17 relative
-    assert np.abs(groups - want2).max() < TOL and np.abs(groups - dense).max() < 3e-5
 
 
 def _padded_batch(rng, cfg, B, L, lo=3):
@@ -538,18 +532,10 @@ def _padded_batch(rng, cfg, B, L, lo=3):
     return ids, mask, lens
 
 
-def _forced_plan(mask, nb=3):
-    """Three length groups regardless of the size heuristic (the tiny test models never reach it)."""
-    lens = (mask != 0).sum(1).cpu().numpy()
-    order = np.argsort(lens, kind="stable")
-    return [(torch.from_numpy(np.ascontiguousarray(p)).to(mask.device), int(lens[p].max())) for p in np.array_split(order, nb) if len(p)]
-
-
 @pytest.mark.parametrize("B", [600, 130, 7])
 def test_dpr_padding_aware_forward_is_bit_identical_to_dense(B, monkeypatch):
-    """Passages padded to max_length like the reference's tokenization_kwargs: the packed forward (real tokens only) and the
-    bucketed forward (groups of similar length, each dense at its own longest length) must both give the dense forward's
-    [CLS] vectors bit for bit."""
+    """Passages padded to max_length like the reference's tokenization_kwargs: the packed forward (real tokens only) must
+    give the dense forward's [CLS] vectors bit for bit."""
     from oracle import encoders as oe
     from viquae_amd import encoders
     cfg = oe.BERT_TINY
@@ -562,22 +548,13 @@ def test_dpr_padding_aware_forward_is_bit_identical_to_dense(B, monkeypatch):
     assert pack is not None and int(pack[0].numel()) == int(lens.sum()) and pack[4].numel() == B
     assert [int(x) for x in pack[2].cpu()[:3]] == [0, int(lens[0]), int(lens[0] + lens[1])]
     packed = model(input_ids=_cuda(ids), attention_mask=_cuda(mask))["pooler_output"]
-    # 2. the grouped forward (MQ_ENC_PACKED=0).  The tiny test model never reaches the size heuristic of _length_buckets
-    #    (tested separately): force three groups
+    # 2. the dense forward
     monkeypatch.setattr(encoders, "_pack_plan", lambda m: None)
-    monkeypatch.setattr(encoders, "_length_buckets", lambda m, max_buckets=8: _forced_plan(m))
-    plan = _forced_plan(_cuda(mask))
-    assert sorted(int(i) for idx, _ in plan for i in idx.cpu()) == list(range(B))
-    assert all(L <= 48 for _, L in plan) and min(L for _, L in plan) < 48
-    fast = model(input_ids=_cuda(ids), attention_mask=_cuda(mask))["pooler_output"]
-    # 3. the dense forward
-    monkeypatch.setattr(encoders, "_length_buckets", lambda m, max_buckets=8: None)
     dense = model(input_ids=_cuda(ids), attention_mask=_cuda(mask))["pooler_output"]
-    assert torch.equal(fast, dense)
     assert torch.equal(packed, dense)
     sub = slice(0, min(B, 40))
     want = oe.bert_forward(state, cfg, ids[sub], None, mask[sub])
-    assert np.abs(fast[sub].cpu().numpy() - want).max() < TOL
+    assert np.abs(packed[sub].cpu().numpy() - want).max() < TOL
 
 
 @pytest.mark.parametrize("gemm", ["split_bf16", "f32"])
@@ -601,7 +578,6 @@ def test_dpr_packed_forward_bert_base_lengths_across_all_attention_classes(gemm,
     assert pack is not None and len(pack[3]) == 3        # three length classes in use
     packed = model(input_ids=_cuda(ids), attention_mask=_cuda(mask), token_type_ids=_cuda(tt))["pooler_output"]
     monkeypatch.setattr(encoders, "_pack_plan", lambda m: None)
-    monkeypatch.setattr(encoders, "_length_buckets", lambda m, max_buckets=8: None)
     dense = model(input_ids=_cuda(ids), attention_mask=_cuda(mask), token_type_ids=_cuda(tt))["pooler_output"]
     assert torch.equal(packed, dense)
     want = oe.bert_forward(state, cfg, ids[:3], tt[:3], mask[:3])
@@ -617,23 +593,28 @@ def test_padding_plan_declines_masks_it_cannot_skip():
     full = np.ones((200, 16), np.int64)               # nothing to skip
     empty = np.ones((200, 16), np.int64)
     empty[3] = 0                                      # an all-masked sequence (HF: uniform attention)
-    big = lambda m: np.tile(m, (40, 4))               # 8000 x 64: large enough for the size heuristic
+    big = lambda m: np.tile(m, (40, 4))               # 8000 x 64
     for m in (left, holes, full, empty):
-        assert encoders._length_buckets(_cuda(big(m))) is None
         assert encoders._pack_plan(_cuda(big(m))) is None
+
+    def covers_every_sequence_once(m):
+        lens = m.sum(1)
+        plan = encoders._pack_plan(_cuda(m))
+        assert plan is not None
+        keep, _, cu, _, cls_rows = plan
+        assert keep.numel() == lens.sum() and cls_rows.numel() == m.shape[0]
+        assert cu.cpu().tolist() == [0] + np.cumsum(lens).tolist()
+
     ok = (np.arange(64)[None] < np.random.default_rng(0).integers(4, 40, 8000)[:, None]).astype(np.int64)
-    plan = encoders._length_buckets(_cuda(ok))
-    assert plan is not None and 1 <= len(plan) <= 8
-    small = encoders._length_buckets(_cuda(ok[:100]))          # small batch: ONE group, cut at its longest length
-    assert small is not None and len(small) == 1 and small[0][1] == int(ok[:100].sum(1).max()) < 64
+    covers_every_sequence_once(ok)
+    covers_every_sequence_once(ok[:100])                       # a small batch
     questions = (np.arange(256)[None] < np.random.default_rng(1).integers(8, 30, 2048)[:, None]).astype(np.int64)
-    plan = encoders._length_buckets(_cuda(questions))          # questions padded to 256 (dpr/questions/config.json)
-    assert plan is not None and max(L for _, L in plan) < 32
-    assert encoders._length_buckets(None) is None
+    covers_every_sequence_once(questions)                      # questions padded to 256 (dpr/questions/config.json)
+    assert encoders._pack_plan(None) is None
 
 
 def test_clip_text_padding_aware_forward_is_bit_identical_to_dense(monkeypatch):
-    """Titles padded to the longest of the batch (CLIP pads with the end-of-text id): grouped-by-length forward == dense."""
+    """Titles padded to the longest of the batch (CLIP pads with the end-of-text id): packed forward == dense."""
     from oracle import encoders as oe
     from viquae_amd import encoders
     cfg = oe.CLIP_TEXT_TINY
@@ -650,14 +631,11 @@ def test_clip_text_padding_aware_forward_is_bit_identical_to_dense(monkeypatch):
     mask = (np.arange(L)[None] < lens[:, None]).astype(np.int64)
     model = encoders.CLIPModel.from_state_dict({"text_config": cfg}, state).to("cuda").eval()
     packed = model.get_text_features(input_ids=_cuda(ids), attention_mask=_cuda(mask))   # default: packed forward
-    monkeypatch.setenv("MQ_ENC_PACKED", "0")
-    monkeypatch.setattr(encoders, "_length_buckets", lambda m, max_buckets=8: _forced_plan(m))
-    fast = model.get_text_features(input_ids=_cuda(ids), attention_mask=_cuda(mask))
-    monkeypatch.setattr(encoders, "_length_buckets", lambda m, max_buckets=8: None)
+    monkeypatch.setenv("MQ_ENC_PAD_SKIP", "0")
     dense = model.get_text_features(input_ids=_cuda(ids), attention_mask=_cuda(mask))
-    assert torch.equal(fast, dense) and torch.equal(packed, dense)
+    assert torch.equal(packed, dense)
     want = oe.clip_text_forward(state, cfg, ids[:32], mask[:32])
-    assert np.abs(fast[:32].cpu().numpy() - want).max() < TOL
+    assert np.abs(packed[:32].cpu().numpy() - want).max() < TOL
 
 
 @pytest.mark.parametrize("gemm", ["split_bf16", "f32"])
@@ -689,8 +667,7 @@ def test_clip_text_packed_forward_vitb32_text_size(gemm, monkeypatch):
     short[5, lens[5] - 1] = 0                 # the mask stops before the end-of-text token of title 5
     cut = model.get_text_features(input_ids=_cuda(ids), attention_mask=_cuda(short))
     assert calls == [1]                       # declined
-    monkeypatch.setenv("MQ_ENC_PACKED", "0")
-    monkeypatch.setattr(encoders, "_length_buckets", lambda m, max_buckets=8: None)
+    monkeypatch.setenv("MQ_ENC_PAD_SKIP", "0")
     dense = model.get_text_features(input_ids=_cuda(ids), attention_mask=_cuda(mask))
     assert torch.equal(packed, dense)
     assert torch.equal(cut, model.get_text_features(input_ids=_cuda(ids), attention_mask=_cuda(short)))

@@ -229,50 +229,25 @@ def test_no_gpu_means_loud_failure():
         idx.add_vectors(np.zeros((4, 8), np.float32))
 
 
-def test_length_partition_is_optimal_and_covers_everything():
-    """_partition_by_length (padding-aware encoder forward): contiguous groups of the ascending lengths, every sequence in
-    exactly one, total padded tokens no worse than equal-count groups and equal to brute force on a small case."""
-    import itertools
-    from viquae_amd.encoders import _partition_by_length
-    rng = np.random.default_rng(0)
-    lens = np.sort(np.clip(rng.normal(130, 30, 2048).astype(int), 8, 256))
-    for nb in (1, 2, 4, 8):
-        parts = _partition_by_length(lens, nb)
-        assert len(parts) <= nb and parts[0].start == 0 and parts[-1].stop == len(lens)
-        assert all(a.stop == b.start for a, b in zip(parts, parts[1:]))
-        cost = sum((p.stop - p.start) * lens[p].max() for p in parts)
-        equal = sum(len(c) * c.max() for c in np.array_split(lens, nb))
-        assert cost <= equal
-    small = np.sort(rng.integers(1, 30, 12))
-    best = min(sum((b - a) * small[a:b].max() for a, b in zip((0,) + cut, cut + (12,)))
-               for r in range(0, 3) for cut in itertools.combinations(range(1, 12), r))
-    got = _partition_by_length(small, 3)
-    assert sum((p.stop - p.start) * small[p].max() for p in got) == best
-    assert _partition_by_length(np.array([5, 5, 5]), 4) == [slice(0, 3)]
-
-
 def test_padding_plan_host_logic_on_cpu_tensors():
-    """_length_buckets is plain tensor logic: right-padded masks with something to cut get a plan that covers every
-    sequence once, each group cut at its longest length; everything else declines."""
+    """_pack_plan is plain tensor logic: a right-padded mask with something to skip gets a plan that covers every sequence
+    once; everything else declines."""
     import torch
-    from viquae_amd.encoders import _length_buckets
+    from viquae_amd.encoders import _pack_plan
     rng = np.random.default_rng(0)
     lens = rng.integers(8, 200, 4000)
     mask = torch.from_numpy((np.arange(256)[None] < lens[:, None]).astype(np.int64))
-    plan = _length_buckets(mask)
-    assert plan is not None and 1 <= len(plan) <= 8
-    seen = np.concatenate([idx.numpy() for idx, _ in plan])
-    assert sorted(seen.tolist()) == list(range(4000))
-    for idx, L in plan:
-        assert L == lens[idx.numpy()].max()
-    assert _length_buckets(torch.ones((4000, 256), dtype=torch.int64)) is None           # nothing to cut
-    assert _length_buckets(mask.flip(1)) is None                                         # left padding
-    assert _length_buckets(None) is None
-    few = _length_buckets(mask[:50])                                                      # small batch: one group at its longest
-    assert few is not None and len(few) == 1 and few[0][1] == lens[:50].max()
+    plan = _pack_plan(mask)
+    assert plan is not None
+    keep, _, cu, _, cls_rows = plan
+    assert keep.numel() == lens.sum() and cls_rows.numel() == 4000
+    assert cu.tolist() == [0] + np.cumsum(lens).tolist()
+    assert _pack_plan(torch.ones((4000, 256), dtype=torch.int64)) is None               # nothing to skip
+    assert _pack_plan(mask.flip(1)) is None                                             # left padding
+    assert _pack_plan(None) is None
     os.environ["MQ_ENC_PAD_SKIP"] = "0"
     try:
-        assert _length_buckets(mask) is None
+        assert _pack_plan(mask) is None
     finally:
         del os.environ["MQ_ENC_PAD_SKIP"]
 

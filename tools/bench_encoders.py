@@ -111,16 +111,9 @@ def dpr_padded_throughput(B=2048, L=256, mean_len=130, std_len=30, steps=2, devi
     ids = torch.randint(1000, 30000, (B, L), generator=g, device=device) * mask
     tt = torch.zeros((B, L), dtype=torch.int64, device=device)
     run = lambda: model(input_ids=ids, token_type_ids=tt, attention_mask=mask)["pooler_output"]  # noqa: E731
-    run()  # builds the weight splits and the side streams
+    run()  # builds the weight splits
     t_skip = time_it(run, steps)
     a = run()
-    os.environ["MQ_ENC_PACKED"] = "0"   # the round-1 forward: <= 8 length groups, each dense at its longest length
-    try:
-        run()
-        t_groups = time_it(run, steps)
-        g_same = bool(torch.equal(a, run()))
-    finally:
-        del os.environ["MQ_ENC_PACKED"]
     os.environ["MQ_ENC_PAD_SKIP"] = "0"
     try:
         t_dense = time_it(run, steps)
@@ -129,9 +122,7 @@ def dpr_padded_throughput(B=2048, L=256, mean_len=130, std_len=30, steps=2, devi
         del os.environ["MQ_ENC_PAD_SKIP"]
     return {"passages_per_s": B / t_skip, "ms_per_batch": t_skip * 1e3, "dense_passages_per_s": B / t_dense,
             "dense_ms_per_batch": t_dense * 1e3, "batch": B, "padded_to": L, "mean_tokens": float(lens.mean()),
-            "identical_to_dense": bool(torch.equal(a, b)), "forward": "packed (real tokens only, attention per sequence)",
-            "length_groups_passages_per_s": B / t_groups, "length_groups_ms_per_batch": t_groups * 1e3,
-            "length_groups_identical": g_same}
+            "identical_to_dense": bool(torch.equal(a, b)), "forward": "packed (real tokens only, attention per sequence)"}
 
 
 def clip_throughput(B=3072, steps=2, device="cuda"):
@@ -253,21 +244,15 @@ def clip_text_padded_throughput(B=2048, mean_len=8, std_len=3, longest=32, steps
     run = lambda: model.get_text_features(input_ids=ids, attention_mask=mask)  # noqa: E731
     t_skip = time_it(run, steps)   # default: the packed forward (real tokens only)
     a = run()
-    os.environ["MQ_ENC_PACKED"] = "0"
-    try:
-        t_groups = time_it(run, steps)   # groups of similar length, each dense at its own length
-        g = run()
-    finally:
-        del os.environ["MQ_ENC_PACKED"]
     os.environ["MQ_ENC_PAD_SKIP"] = "0"
     try:
         t_dense = time_it(run, steps)
         b = run()
     finally:
         del os.environ["MQ_ENC_PAD_SKIP"]
-    return {"titles_per_s": B / t_skip, "ms_per_batch": t_skip * 1e3, "length_groups_titles_per_s": B / t_groups,
+    return {"titles_per_s": B / t_skip, "ms_per_batch": t_skip * 1e3,
             "dense_titles_per_s": B / t_dense, "dense_ms_per_batch": t_dense * 1e3, "batch": B, "padded_to": L,
-            "mean_tokens": float(lens.mean()), "identical_to_dense": bool(torch.equal(a, b) and torch.equal(g, b))}
+            "mean_tokens": float(lens.mean()), "identical_to_dense": bool(torch.equal(a, b))}
 
 
 if __name__ == "__main__":

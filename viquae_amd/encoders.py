@@ -130,10 +130,6 @@ class SplitAct:
         """(hi, lo) as plain [rows, features] int16 tensors"""
         return _untile(self.hi, *self.shape), _untile(self.lo, *self.shape)
 
-    def first_rows(self, B, L):
-        """rows 0, L, 2L, ... (the first token of each of B sequences)"""
-        return self.rows(torch.arange(0, B * L, L, device=self.hi.device))
-
     def rows(self, index):
         """the rows `index` (int64 tensor)"""
         K = self.shape[1]
@@ -310,15 +306,17 @@ class _HipEncoder(nn.Module):
         return getattr(self, name.replace(".", "_"))
 
     def _ws(self, name):
-        """(hi, lo) bf16 split of weight buffer `name`, built once per device (None in f32 mode)."""
+        """(hi, lo) bf16 split of weight buffer `name` in the GEMM tile layout, built once per device.  None in f32 mode and
+        when the split-bf16 kernels cannot take the weight (K % 32 != 0: gemm_nt runs the fp32 GEMM)."""
         if _gemm_mode() != "split_bf16":
             return None
         w = getattr(self, name)
+        if w.dim() != 2 or w.shape[1] % 32:
+            return None
         cache = self.__dict__.setdefault("_split_cache", {})
         key = (name, w.device, w.data_ptr())
-        if key not in cache:  # tile layout whenever the split-bf16 kernels can take the weight at all (K % 32 == 0)
-            tiled = w.dim() == 2 and w.shape[1] % 32 == 0 and os.environ.get("MQ_ENC_W_TILED", "1") != "0"
-            cache[key] = split_bf16_tiled(w) if tiled else split_bf16(w)
+        if key not in cache:
+            cache[key] = split_bf16_tiled(w)
         return cache[key]
 
 
@@ -416,138 +414,50 @@ class BertEncoderHIP(_HipEncoder):
         """The encoder stack over PACKED embeddings h [T, H] (hs = their split pair in split mode, or None to make it here):
         sequence b = rows [cu[b], cu[b + 1]), attention per sequence (``classes`` of :func:`pack_plan_from_lengths`) -> the
         rows ``cls_rows`` of the last layer's output, [B, H]."""
-        H = self.hidden
-        split = self.uses_split()
-        if split and hs is None:
-            hs = SplitAct(*split_bf16_tiled(h), shape=h.shape)
-        scale = 1.0 / math.sqrt(H // self.heads)
-        for i in range(self.layers):
-            w = lambda n: getattr(self, f"l{i}_{n}")  # noqa: E731
-            sp = lambda n: self._ws(f"l{i}_{n}")  # noqa: E731
-            last = i == self.layers - 1
-            if split:
-                qkv = gemm_nt(hs, w("wqkv"), w("bqkv"), None, EPI_BIAS, wsplit=sp("wqkv"))
-                ctx = attention_packed(qkv, cu, classes, self.heads, scale, split=True)
-                pair_res = _pair_residual()  # see _layers
-                if last:  # everything after the last attention is row-wise: only the [CLS] rows go on
-                    ctx, h = ctx.rows(cls_rows), (h.index_select(0, cls_rows).contiguous() if h is not None else None)
-                    hs = hs.rows(cls_rows)
-                a = gemm_nt(ctx, w("wo"), w("bo"), hs if pair_res else h, EPI_BIAS_RESIDUAL, wsplit=sp("wo"))
-                h1, h1s = layernorm_split(a, w("g1"), w("b1"), self.eps, f32_out=a, want_f32=not pair_res)
-                f = gemm_nt(h1s, w("wi"), w("bi"), None, EPI_BIAS_GELU, wsplit=sp("wi"), out_split=True)
-                o = gemm_nt(f, w("w2"), w("b2"), h1s if pair_res else h1, EPI_BIAS_RESIDUAL, wsplit=sp("w2"))
-                h, hs = layernorm_split(o, w("g2"), w("b2n"), self.eps, f32_out=o, want_f32=not pair_res or last)
-            else:
-                qkv = gemm_nt(h, w("wqkv"), w("bqkv"), None, EPI_BIAS, wsplit=sp("wqkv"))
-                ctx = attention_packed(qkv, cu, classes, self.heads, scale)
-                if last:
-                    ctx, h = ctx.index_select(0, cls_rows).contiguous(), h.index_select(0, cls_rows).contiguous()
-                a = gemm_nt(ctx, w("wo"), w("bo"), h, EPI_BIAS_RESIDUAL, wsplit=sp("wo"))
-                h1 = layernorm(a, w("g1"), w("b1"), self.eps, out=a)
-                f = gemm_nt(h1, w("wi"), w("bi"), None, EPI_BIAS_GELU, wsplit=sp("wi"))
-                o = gemm_nt(f, w("w2"), w("b2"), h1, EPI_BIAS_RESIDUAL, wsplit=sp("w2"))
-                h = layernorm(o, w("g2"), w("b2n"), self.eps, out=o)
-        return h
+        scale = 1.0 / math.sqrt(self.hidden // self.heads)
+        attend = lambda qkv, split: attention_packed(qkv, cu, classes, self.heads, scale, split=split)  # noqa: E731
+        return self._stack(h, hs, attend, cls_rows)
 
     @torch.no_grad()
     def _layers(self, h, hs, mask, B, L, output_hidden_states=False, cls_only=False):
         """The encoder stack over embeddings h [B*L, H] (hs = their split pair in split mode, or None to make it here)
-        with an int64 0/1 mask [B, L] -> (last hidden [B, L or 1, H], hidden states or None)."""
+        with an int64 0/1 mask [B, L] -> (last hidden [B, L or 1, H], hidden states or None).  ``cls_only``: DPR reads only
+        last_hidden_state[:, 0], so only the first row of every sequence leaves the last layer."""
         H = self.hidden
-        split = self.uses_split()
-        if split and hs is None:
-            hs = SplitAct(*split_bf16_tiled(h), shape=h.shape)  # the tile layout of the weights IS the pair layout
-        hidden = [h.view(B, L, H)] if output_hidden_states else None
         scale = 1.0 / math.sqrt(H // self.heads)
+        attend = lambda qkv, split: attention(qkv, mask, B, L, self.heads, scale, split=split)  # noqa: E731
+        keep = torch.arange(0, B * L, L, device=h.device) if cls_only else None
+        hidden = [h] if output_hidden_states else None
+        h = self._stack(h, hs, attend, keep, hidden)
+        if hidden is not None:
+            hidden = [x.view(B, L, H) for x in hidden]
+        return h.view(B, 1 if cls_only else L, H), hidden
+
+    def _stack(self, h, hs, attend, keep_rows, hidden=None):
+        """The layers of :func:`_bert_block` over h [rows, H]; ``keep_rows`` selects the rows that leave the last layer and
+        ``hidden`` (a list) collects every layer's output -> the last layer's output."""
+        if hs is None and self.uses_split():
+            hs = SplitAct(*split_bf16_tiled(h), shape=h.shape)  # the tile layout of the weights IS the pair layout
         for i in range(self.layers):
             w = lambda n: getattr(self, f"l{i}_{n}")  # noqa: E731
             sp = lambda n: self._ws(f"l{i}_{n}")  # noqa: E731
-            last_cls = cls_only and i == self.layers - 1
-            if split:
-                qkv = gemm_nt(hs, w("wqkv"), w("bqkv"), None, EPI_BIAS, wsplit=sp("wqkv"))
-                ctx = attention(qkv, mask, B, L, self.heads, scale, split=True)
-                if last_cls:
-                    # DPR reads only last_hidden_state[:, 0]: after the last attention, the output projection, both
-                    # LayerNorms and the FFN are row-wise, so run them on the [CLS] rows alone (same numbers, 1/L of the rows)
-                    ctx = ctx.first_rows(B, L)
-                    h = h.view(B, L, H)[:, 0, :].contiguous() if h is not None else None
-                    hs = hs.first_rows(B, L)
-                # Shortcuts read the LayerNorm outputs from their (hi, lo) pairs (value hi + lo: 16 mantissa bits, 2^-17 relative),
-                # so a LayerNorm writes the pair only -- a third less traffic per LayerNorm (MQ_ENC_RESIDUAL=f32: the fp32 copies)
-                pair_res = _pair_residual()
-                a = gemm_nt(ctx, w("wo"), w("bo"), hs if pair_res else h, EPI_BIAS_RESIDUAL, wsplit=sp("wo"))
-                h1, h1s = layernorm_split(a, w("g1"), w("b1"), self.eps, f32_out=a, want_f32=not pair_res)
-                f = gemm_nt(h1s, w("wi"), w("bi"), None, EPI_BIAS_GELU, wsplit=sp("wi"), out_split=True)
-                o = gemm_nt(f, w("w2"), w("b2"), h1s if pair_res else h1, EPI_BIAS_RESIDUAL, wsplit=sp("w2"))
-                need_f32 = not pair_res or output_hidden_states or i == self.layers - 1
-                h, hs = layernorm_split(o, w("g2"), w("b2n"), self.eps, f32_out=o, want_f32=need_f32)
-            else:
-                qkv = gemm_nt(h, w("wqkv"), w("bqkv"), None, EPI_BIAS, wsplit=sp("wqkv"))
-                ctx = attention(qkv, mask, B, L, self.heads, scale)
-                if last_cls:
-                    ctx = ctx.view(B, L, H)[:, 0, :].contiguous()
-                    h = h.view(B, L, H)[:, 0, :].contiguous()
-                a = gemm_nt(ctx, w("wo"), w("bo"), h, EPI_BIAS_RESIDUAL, wsplit=sp("wo"))
-                h1 = layernorm(a, w("g1"), w("b1"), self.eps, out=a)
-                f = gemm_nt(h1, w("wi"), w("bi"), None, EPI_BIAS_GELU, wsplit=sp("wi"))
-                o = gemm_nt(f, w("w2"), w("b2"), h1, EPI_BIAS_RESIDUAL, wsplit=sp("w2"))
-                h = layernorm(o, w("g2"), w("b2n"), self.eps, out=o)
-            if output_hidden_states:
-                hidden.append(h.view(B, L, H))
-        if cls_only:
-            return h.view(B, 1, H), hidden
-        return h.view(B, L, H), hidden
-
-
-_SIDE_STREAMS = {}
-
-
-def _side_streams(device, n):
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-    have = _SIDE_STREAMS.setdefault(key, [])
-    while len(have) < n:
-        have.append(torch.cuda.Stream(device=device))
-    return have[:n]
-
-
-def _length_buckets(attention_mask, max_buckets=8):
-    """[(int64 sequence indices on the device, length)] for a right-padded 0/1 mask with padding worth skipping, else
-    None (no mask, other mask shapes, empty sequences, nothing to gain, or MQ_ENC_PAD_SKIP=0).  One small D2H copy."""
-    if attention_mask is None or os.environ.get("MQ_ENC_PAD_SKIP", "1") == "0":
-        return None
-    B, L = attention_mask.shape
-    if B == 0 or L < 2:
-        return None
-    m = attention_mask != 0
-    right_padded = bool((m[:, 1:] <= m[:, :-1]).all()) and bool(((attention_mask == 0) | (attention_mask == 1)).all())
-    if not right_padded:
-        return None
-    lens = m.sum(dim=1).cpu().numpy()
-    if lens.min() < 1 or int(lens.sum()) > 0.9 * B * L:
-        return None
-    # a group must still fill the chip (its GEMMs have real_tokens / 256 row tiles): ~32 k tokens each, else the dense
-    # forward of a small batch is already one wave of workgroups and splitting it only adds launches
-    nb = int(max(1, min(max_buckets, lens.sum() // 32768)))
-    if nb == 1 and int(lens.max()) > 0.9 * L:
-        return None  # one group at (nearly) the padded length: nothing to gain
-    order = np.argsort(lens, kind="stable")
-    plan = []
-    for part in _partition_by_length(lens[order], nb):
-        seqs = order[part]
-        plan.append((torch.from_numpy(np.ascontiguousarray(seqs)).to(attention_mask.device), int(lens[seqs].max())))
-    return plan
+            last = i == self.layers - 1
+            h, hs = _bert_block(h, hs, w, sp, attend, self.eps, keep_rows if last else None, hidden is not None or last)
+            if hidden is not None:
+                hidden.append(h)
+        return h
 
 
 def _pack_plan(attention_mask):
     """(kept flat token indices, position id per kept token, cu_seqlens, attention launch classes, [CLS] rows) for a
     right-padded 0/1 mask with padding worth skipping -- else None (no mask, other mask shapes, empty sequences,
-    < 10 % padding, or MQ_ENC_PACKED=0).  One small D2H copy (the lengths).
+    < 10 % padding, or MQ_ENC_PAD_SKIP=0).  One small D2H copy (the lengths).
 
     Packed forward: the reference pads every passage to max_length (256, experiments/ir/viquae/dpr/passages/config.json:11-14)
     although a 100-word passage has ~130 tokens.  Every operation of the encoder is row-wise except attention, and in
     attention a padded key contributes exactly 0 to every sum and never sets a row maximum: dropping the padded ROWS
     everywhere and the padded KEYS in attention leaves the [CLS] vectors bit-identical to the dense forward."""
-    if attention_mask is None or os.environ.get("MQ_ENC_PACKED", "1") == "0" or os.environ.get("MQ_ENC_PAD_SKIP", "1") == "0":
+    if attention_mask is None:
         return None
     B, L = attention_mask.shape
     if B == 0 or L < 2:
@@ -567,7 +477,7 @@ def pack_plan_from_lengths(lens, L, device, stage=None):
     stream while batch i runs (viquae_amd/pipeline.py).  ``stage`` (optional): numpy array -> page-locked CPU tensor holding a
     copy of it; the copies to the device are then truly asynchronous (a copy from pageable memory blocks the calling thread,
     on this runtime until the device has drained).  None when packing does not pay (see _pack_plan)."""
-    if os.environ.get("MQ_ENC_PACKED", "1") == "0" or os.environ.get("MQ_ENC_PAD_SKIP", "1") == "0":
+    if os.environ.get("MQ_ENC_PAD_SKIP", "1") == "0":
         return None
     lens = np.asarray(lens, dtype=np.int64)
     B = lens.shape[0]
@@ -591,30 +501,6 @@ def pack_plan_from_lengths(lens, L, device, stage=None):
             classes.append((dev(sel), int(lens[sel].max())))
     cls_rows = dev(cu_host[:-1].astype(np.int64))
     return keep, pos, cu, classes, cls_rows
-
-
-def _partition_by_length(sorted_lens, nb):
-    """Cuts ascending lengths into <= nb contiguous groups minimising sum(group size x group's longest length), the
-    tokens a dense forward of each group processes (dynamic programme over the distinct lengths) -> list of slices."""
-    u, cnt = np.unique(sorted_lens, return_counts=True)
-    U = len(u)
-    nb = max(1, min(nb, U))
-    cs = np.concatenate([[0], np.cumsum(cnt)])
-    cost = np.full((nb + 1, U + 1), np.inf)
-    cost[0, 0] = 0.0
-    arg = np.zeros((nb + 1, U + 1), dtype=np.int64)
-    for b in range(1, nb + 1):
-        for j in range(1, U + 1):
-            c = cost[b - 1, :j] + (cs[j] - cs[:j]) * float(u[j - 1])  # last group = distinct lengths i .. j-1
-            i = int(np.argmin(c))
-            cost[b, j], arg[b, j] = c[i], i
-    b = int(np.argmin(cost[1:, U])) + 1
-    cuts, j = [], U
-    while b > 0:
-        i = int(arg[b, j])
-        cuts.append(slice(int(cs[i]), int(cs[j])))
-        j, b = i, b - 1
-    return [c for c in reversed(cuts) if c.stop > c.start]
 
 
 class _DPREncoder(_HipEncoder):
@@ -648,64 +534,11 @@ class _DPREncoder(_HipEncoder):
         pack = None if output_hidden_states else (pack_plan if pack_plan is not None else _pack_plan(attention_mask))
         if pack is not None:
             return ModelOutput(pooler_output=self.bert_model.forward_packed(input_ids, token_type_ids, pack))
-        plan = None if output_hidden_states else _length_buckets(attention_mask)
-        if plan is not None:
-            return ModelOutput(pooler_output=self._forward_buckets(plan, input_ids, attention_mask, token_type_ids))
         last, hidden = self.bert_model(input_ids, token_type_ids, attention_mask, output_hidden_states, cls_only=True)
         out = ModelOutput(pooler_output=last[:, 0, :].contiguous())
         if output_hidden_states:
             out["hidden_states"] = tuple(hidden)
         return out
-
-    def _forward_buckets(self, plan, input_ids, attention_mask, token_type_ids):
-        return _pooled_by_groups(self.bert_model, plan, input_ids, attention_mask, token_type_ids)
-
-
-def _pooled_by_groups(bert, plan, input_ids, attention_mask, token_type_ids=None, embeddings=None):
-    """Padding-aware forward: the batch is cut into a few groups of similar length, each run dense at ITS longest
-    length.  The reference pads every passage to 256 tokens (experiments/ir/viquae/dpr/passages/config.json:11-14:
-    ``padding: max_length``) although a 100-word passage has ~130: about half of the dense work is padding.  Every
-    operation is row-wise except attention, where a masked key contributes exactly 0 to every sum and never to the
-    row maximum -- so the pooled [CLS] vectors are bit-identical to the dense forward (asserted in the tests).
-    ``embeddings`` [B, L, H] (ECA: text + face + image tokens) replaces the token ids when given."""
-    ref = embeddings if embeddings is not None else input_ids
-    B, dev = ref.shape[0], ref.device
-    out = torch.empty((B, bert.hidden), dtype=torch.float32, device=dev)
-    # groups alternate between two side streams: the tail of one group's GEMM (a partial wave of workgroups) is
-    # filled by the other group's kernels
-    main = torch.cuda.current_stream(dev)
-    streams = _side_streams(dev, min(int(os.environ.get("MQ_ENC_GROUP_STREAMS", "2")), len(plan)))
-    ready = torch.cuda.Event()
-    ready.record(main)
-
-    def run(idx, Li):
-        mask = attention_mask.index_select(0, idx)[:, :Li].contiguous()
-        if embeddings is not None:
-            h = embeddings.index_select(0, idx)[:, :Li].contiguous()
-            last, _ = bert._layers(h.view(-1, bert.hidden), None, mask, idx.numel(), Li, False, cls_only=True)
-        else:
-            ids = input_ids.index_select(0, idx)[:, :Li]
-            tt = token_type_ids.index_select(0, idx)[:, :Li] if token_type_ids is not None else None
-            last, _ = bert(ids, tt, mask, False, cls_only=True)
-        out.index_copy_(0, idx, last[:, 0, :])
-
-    first = 0
-    warm_key = (str(dev), bert.w_word.data_ptr(), _gemm_mode())
-    if bert.__dict__.get("_weights_split") != warm_key:
-        # the (hi, lo) weight splits are built lazily by the first forward: build them on the caller's stream before
-        # two other streams start reading them
-        run(*plan[0])
-        first = 1
-        ready.record(main)
-        bert.__dict__["_weights_split"] = warm_key
-    for n, (idx, Li) in enumerate(plan[first:]):
-        st = streams[n % len(streams)]
-        st.wait_event(ready)
-        with torch.cuda.stream(st):
-            run(idx, Li)
-    for st in streams:
-        main.wait_stream(st)
-    return out
 
 
 class DPRContextEncoder(_DPREncoder):
@@ -716,6 +549,37 @@ class DPRContextEncoder(_DPREncoder):
 class DPRQuestionEncoder(_DPREncoder):
     """transformers.DPRQuestionEncoder (experiments/ir/viquae/dpr/questions/config.json)."""
     _prefix = "question_encoder.bert_model."
+
+
+def _bert_block(h, hs, w, sp, attend, eps, keep_rows=None, need_f32=True):
+    """One post-LN BERT layer on h [rows, H] -> (h, hs).  In split mode ``hs`` is the (hi, lo) pair of h (h itself may be None
+    when the shortcuts read the pairs); in fp32 mode hs is None.  ``attend(qkv, split)`` runs the dense or the packed
+    attention.  ``keep_rows`` (int64 row indices) is given for the LAST layer: after the attention everything is row-wise, so
+    the output projection, both LayerNorms and the FFN run on those rows alone (same numbers).  ``need_f32``: the caller
+    reads the fp32 output h of this layer."""
+    if hs is not None:
+        qkv = gemm_nt(hs, w("wqkv"), w("bqkv"), None, EPI_BIAS, wsplit=sp("wqkv"))
+        ctx = attend(qkv, True)
+        if keep_rows is not None:
+            ctx, hs = ctx.rows(keep_rows), hs.rows(keep_rows)
+            h = h.index_select(0, keep_rows).contiguous() if h is not None else None
+        # Shortcuts read the LayerNorm outputs from their (hi, lo) pairs (value hi + lo: 16 mantissa bits, 2^-17 relative),
+        # so a LayerNorm writes the pair only -- a third less traffic per LayerNorm (MQ_ENC_RESIDUAL=f32: the fp32 copies)
+        pair_res = _pair_residual()
+        a = gemm_nt(ctx, w("wo"), w("bo"), hs if pair_res else h, EPI_BIAS_RESIDUAL, wsplit=sp("wo"))
+        h1, h1s = layernorm_split(a, w("g1"), w("b1"), eps, f32_out=a, want_f32=not pair_res)
+        f = gemm_nt(h1s, w("wi"), w("bi"), None, EPI_BIAS_GELU, wsplit=sp("wi"), out_split=True)
+        o = gemm_nt(f, w("w2"), w("b2"), h1s if pair_res else h1, EPI_BIAS_RESIDUAL, wsplit=sp("w2"))
+        return layernorm_split(o, w("g2"), w("b2n"), eps, f32_out=o, want_f32=not pair_res or need_f32)
+    qkv = gemm_nt(h, w("wqkv"), w("bqkv"), None, EPI_BIAS, wsplit=sp("wqkv"))
+    ctx = attend(qkv, False)
+    if keep_rows is not None:
+        ctx, h = ctx.index_select(0, keep_rows).contiguous(), h.index_select(0, keep_rows).contiguous()
+    a = gemm_nt(ctx, w("wo"), w("bo"), h, EPI_BIAS_RESIDUAL, wsplit=sp("wo"))
+    h1 = layernorm(a, w("g1"), w("b1"), eps, out=a)
+    f = gemm_nt(h1, w("wi"), w("bi"), None, EPI_BIAS_GELU, wsplit=sp("wi"))
+    o = gemm_nt(f, w("w2"), w("b2"), h1, EPI_BIAS_RESIDUAL, wsplit=sp("w2"))
+    return layernorm(o, w("g2"), w("b2n"), eps, out=o), None
 
 
 # --------------------------------------------------------------------------------------------------
@@ -878,17 +742,7 @@ class CLIPModel(_HipEncoder):
         pack = _pack_plan(attention_mask)
         if pack is not None and bool((eot.to(torch.int64) < attention_mask.to(torch.int64).sum(dim=1)).all()):
             return self._text_features_packed(ids, eot, pack)
-        plan = _length_buckets(attention_mask)
-        if plan is not None:
-            # titles padded to the longest of 2048 (experiments/ir/viquae/clip/config.json:10-13) are mostly padding: run
-            # groups of similar length at their own length -- the pooled end-of-text row only attends to real tokens, so
-            # the features are bit-identical to the dense forward
-            out = torch.empty((B, self.t_wproj.shape[0]), dtype=torch.float32, device=ids.device)
-            for idx, Li in plan:
-                out.index_copy_(0, idx, self._text_features_dense(ids.index_select(0, idx)[:, :Li].contiguous(),
-                                                                  attention_mask.index_select(0, idx)[:, :Li]))
-            return out
-        return self._text_features_dense(ids, attention_mask)
+        return self._text_features_dense(ids, attention_mask)  # also a mask that stops before a title's end-of-text token
 
     def _text_features_packed(self, ids, eot, pack):
         """Packed forward of right-padded titles (``pack`` from :func:`_pack_plan`): only the real tokens go through the
@@ -1114,7 +968,7 @@ class ECAEncoder(_MMEmbeddings):
         if not output_hidden_states and return_dict and os.environ.get("MQ_ENC_PAD_SKIP", "1") != "0" and bool((full_mask[:, 0] != 0).all()):
             # The text is padded to max_length in the MIDDLE of the joint sequence (text | faces | images).  The layers are
             # permutation-equivariant (positions were added by the embeddings), so the attended tokens are moved to the
-            # front in their original order ([CLS] stays row 0) and the padding-aware forward applies.  Masked keys add
+            # front in their original order ([CLS] stays row 0) and the packed forward applies.  Masked keys add
             # exact zeros, but the surviving keys sit in other MFMA k-groups: equal to the dense forward up to fp32
             # summation order (~1e-6), not bit for bit.
             order = torch.argsort((full_mask == 0).to(torch.int8), dim=1, stable=True)
@@ -1126,11 +980,6 @@ class ECAEncoder(_MMEmbeddings):
                 keep, _, cu, classes, cls_rows = pack
                 flat = (order + torch.arange(B, device=dev)[:, None] * Lt).reshape(-1).index_select(0, keep)
                 pooled = bert.packed_layers(h.view(B * Lt, H).index_select(0, flat), None, cu, classes, cls_rows)
-                return ModelOutput(pooler_output=pooled, last_hidden_state=pooled[:, None, :], hidden_states=None, attentions=None)
-            plan = _length_buckets(cmask)
-            if plan is not None:
-                hc = torch.gather(h, 1, order[:, :, None].expand(-1, -1, H))
-                pooled = _pooled_by_groups(bert, plan, None, cmask, embeddings=hc)
                 return ModelOutput(pooler_output=pooled, last_hidden_state=pooled[:, None, :], hidden_states=None, attentions=None)
         last, hidden = bert._layers(h.view(B * Lt, H), None, full_mask, B, Lt, output_hidden_states, cls_only=not output_hidden_states)
         pooled = last[:, 0, :]
@@ -1170,12 +1019,8 @@ class IntermediateLinearFusion(_MMEmbeddings):
         mmc = self.mm
         lib = _lib.load()
         pack = _pack_plan(text_inputs.get("attention_mask"))
-        plan = None if pack is not None else _length_buckets(text_inputs.get("attention_mask"))
         if pack is not None:     # the DPR encoders' packed forward: real tokens only, bit-identical [CLS] rows
             pooled = self.bert_model.forward_packed(text_inputs["input_ids"], text_inputs.get("token_type_ids"), pack)
-        elif plan is not None:
-            pooled = _pooled_by_groups(self.bert_model, plan, text_inputs["input_ids"], text_inputs["attention_mask"],
-                                       text_inputs.get("token_type_ids"))
         else:
             last, _ = self.bert_model(text_inputs["input_ids"], text_inputs.get("token_type_ids"),
                                       text_inputs.get("attention_mask"), cls_only=True)

@@ -19,6 +19,7 @@ runtime as page-locked, which makes the host -> device copy of a packed batch a 
 GPU.  A worker reproduces `meerqat.data.loading.load_image` (:108-119): unreadable or empty images are reported and become
 `None` in the output, with the same warning text issued by the parent."""
 import errno
+import gc
 import mmap
 import multiprocessing as mp
 import os
@@ -152,13 +153,19 @@ class DecodePool:
         self.tensors = [torch.frombuffer(m, dtype=torch.uint8) for m in self.maps]
         ctx = mp.get_context("fork")
         self.conns, self.procs = [], []
-        for _ in range(max(1, int(n_procs))):
-            parent, child = ctx.Pipe()
-            p = ctx.Process(target=_worker, args=(child, self.maps), daemon=True)
-            p.start()
-            child.close()
-            self.conns.append(parent)
-            self.procs.append(p)
+        # the children must never collect the objects they inherit: a finaliser of a GPU tensor or event calls the GPU runtime,
+        # which does not survive the fork (a collection in the child crashed the worker)
+        gc.freeze()
+        try:
+            for _ in range(max(1, int(n_procs))):
+                parent, child = ctx.Pipe()
+                p = ctx.Process(target=_worker, args=(child, self.maps), daemon=True)
+                p.start()
+                child.close()
+                self.conns.append(parent)
+                self.procs.append(p)
+        finally:
+            gc.unfreeze()
         # page-lock the slots AFTER the fork (MQ_IMAGE_PIN=0: leave them pageable): the children only ever see plain shared
         # memory, and the fork never meets a registered range of THIS mapping
         self.pinned = []
