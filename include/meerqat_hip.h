@@ -608,7 +608,9 @@ int mq_im2col_split_f32(const float *x_dev, int B, int H, int W, int C, int nchw
  *                 scale_dev / shift_dev [N] are given, P = split(Y * scale + shift) (the BatchNorm in front of the NEXT convolution)
  *   Ph / Pl       pair output, PAIR LAYOUT over [M, N], mq_split_bf16_tiled_elems(M, N) elements each
  *   zeros_dev     at least 16 bytes of zeros on the device (the padded border's source)
- *   tile          MQ_CONV_TILE_AUTO, or one of the workgroup tiles (rows x columns; the column count must divide N) */
+ *   tile          MQ_CONV_TILE_AUTO, or one of the workgroup tiles (rows x columns; the column count must divide N).  AUTO takes
+ *                 MQ_CONV_TILE_PATCH_256x64 for N = 64 at stride 1 with MQ_CONV_K_CHANNEL_MAJOR and W <= 127, otherwise the
+ *                 widest tile the channel count fills while it still gives every CU a workgroup */
 #define MQ_CONV_TILE_AUTO 0
 #define MQ_CONV_TILE_256x256 1
 #define MQ_CONV_TILE_512x128 2
@@ -647,8 +649,7 @@ int mq_stem_conv3x3_f32(const float *x_dev, int B, int H, int W, const float *wt
  *   prelu_slope_dev != NULL:  P = r(prelu(t))                                        (residual, Y, scale, shift must be NULL)
  *   prelu_slope_dev == NULL:  Y = r(t + residual) (fp16 [M, N]: the next shortcut), and, when scale_dev / shift_dev [N] are given,
  *                 P = r(Y * scale + shift) (the next block's bn1)
- *   tile          as for mq_conv3x3_pair_f32 (MQ_CONV_TILE_PATCH_256x64 needs MQ_CONV_K_CHANNEL_MAJOR); AUTO takes the patch tile
- *                 for N = 64 at stride 1 with MQ_CONV_K_CHANNEL_MAJOR
+ *   tile          as for mq_conv3x3_pair_f32 (MQ_CONV_TILE_PATCH_256x64 needs MQ_CONV_K_CHANNEL_MAJOR)
  * mq_stem_conv3x3_f16: the stem (3 -> 64, 3 x 3, stride 1, padding 1) on the vector ALU: r(x) * wt (wt fp32 [27, 64] holding the
  *   fp16 weights, row (kh * 3 + kw) * 3 + c), fp32 accumulation; v = r(prelu(r(r(acc) * post_scale + post_shift)));
  *   P = r(v * scale + shift) [B * H * W, 64] (the first block's bn1);  D = v at even (h, w) [B * H/2 * W/2, 64] (D may be NULL).

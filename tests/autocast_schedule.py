@@ -7,9 +7,11 @@ everything up to ``flatten`` under ``torch.cuda.amp.autocast``, ``fc`` and ``fea
     residual add                  fp16 + fp16                                                    -> rounded to fp16
     bn2 -> flatten                fp16, then .float(); fc, features in fp32
 
-``r`` rounds to fp16 (nearest even, overflow to +-inf) and returns the working dtype: float32 states the schedule as the golden
-file's ``embeddings_fp16_autocast`` was made, float64 puts exact arithmetic between the same roundings (the per-kernel pins of
-tests/test_arcface_fp16_gpu.py)."""
+``r`` rounds to fp16 (nearest even, overflow to +-inf) and returns the working dtype.  ``forward`` computes every operation in
+float64 and rounds its result to ``dtype`` before fp16: float32 is correctly rounded fp32 between the roundings, as the golden
+file's ``embeddings_fp16_autocast`` was made -- the same bits on every CPU, where torch's own fp32 convolutions and BatchNorms
+sum and fuse differently per instruction set and one flipped fp16 rounding cascades through 50 layers; float64 puts exact
+arithmetic between the same roundings (the per-kernel pins of tests/test_arcface_fp16_gpu.py)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -47,19 +49,23 @@ def ulp16(v):
 
 
 def forward(state, x, dtype=torch.float32):
-    """IResNet-50 eval forward at the autocast rounding points; state: checkpoint-layout dict of tensors, x: [B, 3, 112, 112]"""
-    st = {k: v.to(dtype) for k, v in state.items()}
-    x = x.to(dtype)
+    """IResNet-50 eval forward at the autocast rounding points; state: checkpoint-layout dict of tensors, x: [B, 3, 112, 112];
+    every operation in float64, its result rounded to ``dtype`` (then to fp16 in the backbone)"""
+    st = {k: v.to(torch.float64) for k, v in state.items()}
+    x = x.to(torch.float64)
+
+    def q(t):
+        return t.to(dtype).to(torch.float64)
 
     def norm(t, name):
-        return r(F.batch_norm(t, st[name + ".running_mean"], st[name + ".running_var"], st[name + ".weight"], st[name + ".bias"],
-                              training=False, momentum=0.0, eps=1e-5))
+        return r(q(F.batch_norm(t, st[name + ".running_mean"], st[name + ".running_var"], st[name + ".weight"], st[name + ".bias"],
+                                training=False, momentum=0.0, eps=1e-5)))
 
     def conv(t, name, stride, padding):
-        return r(F.conv2d(t, r(st[name + ".weight"]), None, stride=stride, padding=padding))
+        return r(q(F.conv2d(t, r(st[name + ".weight"]), None, stride=stride, padding=padding)))
 
     def act(t, name):
-        return r(F.prelu(t, r(st[name + ".weight"])))
+        return r(q(F.prelu(t, r(st[name + ".weight"]))))
 
     t = act(norm(conv(r(x), "conv1", 1, 1), "bn1"), "prelu")
     for s, (blocks, _) in enumerate(STAGES, start=1):
@@ -71,8 +77,8 @@ def forward(state, x, dtype=torch.float32):
             u = norm(conv(u, p + ".conv2", stride, 1), p + ".bn3")
             if b == 0:
                 t = norm(conv(t, p + ".downsample.0", stride, 0), p + ".downsample.1")
-            t = r(u + t)
-    t = torch.flatten(norm(t, "bn2"), 1).to(torch.float32).to(dtype)
-    t = F.linear(t, st["fc.weight"], st["fc.bias"])
+            t = r(q(u + t))
+    t = torch.flatten(norm(t, "bn2"), 1)
+    t = q(F.linear(t, st["fc.weight"], st["fc.bias"]))
     return F.batch_norm(t, st["features.running_mean"], st["features.running_var"], st["features.weight"], st["features.bias"],
-                        training=False, momentum=0.0, eps=1e-5)
+                        training=False, momentum=0.0, eps=1e-5).to(dtype)

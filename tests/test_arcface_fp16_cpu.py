@@ -57,6 +57,8 @@ def test_precision_is_validated(monkeypatch):
     want = torch.from_numpy(w.transpose(0, 2, 3, 1).reshape(64, -1).astype(np.float16))
     from viquae_amd.encoders import _untile
     assert torch.equal(_untile(m.layer1_0_conv1_w16, 64, 576).view(torch.float16), want)  # unfolded: bn2 is not in the weights
+    # an fp16 model holds the weights of its own precision only: of the folded fp32 weights and biases, only the shared head's
+    assert {n for n, _ in m.named_buffers() if n.endswith(("_w2", "_b"))} == {"fc_w2", "fc_b"}
     for bad in ("bf16", "FP16", None, 16):
         with pytest.raises(ValueError):
             ArcFaceR50(state, precision=bad)

@@ -13,8 +13,9 @@ arcface_torch**; what this script pins is the restatement's arithmetic against t
 It also measures what the reference's `fp16=True` costs: under `torch.cuda.amp.autocast` every convolution / PReLU of the
 backbone runs in half precision with fp32 accumulation, BatchNorm and the residual add take and return half tensors, and the head
 (`fc` + `features`) runs in fp32 on `x.float()`.  That is emulated here by rounding the convolution weights and EVERY
-intermediate tensor of the backbone to fp16 (computation in fp32 between the roundings) -- max |fp32 - fp16-autocast| over the
-same faces is recorded in the golden file and quoted in DESIGN.md section 2.
+intermediate tensor of the backbone to fp16 (correctly rounded fp32 between the roundings: float64 arithmetic rounded to fp32, as
+torch's own fp32 operators give other bits per instruction set) -- max |fp32 - fp16-autocast| over the same faces is recorded in
+the golden file and quoted in DESIGN.md section 2.
 
 Runs in the build container only (torch-CPU); commits inputs + outputs only:
     python tools/make_golden_arcface.py        ->  tests/golden/arcface_r50_8.npz
@@ -42,7 +43,9 @@ def faces_from_bytes(u8):
 def torch_iresnet50(state, x, half=False):
     """IResNet-50 forward in eval mode over a checkpoint-layout state dict of torch tensors.  ``half``: emulate the
     reference's fp16 autocast (see the module docstring)."""
-    r = (lambda t: t.to(torch.float16).to(torch.float32)) if half else (lambda t: t)
+    if half:   # float64 arithmetic, every result rounded to fp32 (correctly rounded: the same bits on every CPU) and then to fp16
+        state, x = {k: v.double() for k, v in state.items()}, x.double()
+    r = (lambda t: t.to(torch.float32).to(torch.float16).to(torch.float64)) if half else (lambda t: t)
 
     def norm(t, name):
         return r(F.batch_norm(t, state[name + ".running_mean"], state[name + ".running_var"], state[name + ".weight"],

@@ -17,10 +17,10 @@ convolution that PRODUCES a tensor.  An IBasicBlock is two launches:
 (+ im2col and GEMM for the strided 1 x 1 downsample of a stage's first block).  The 3-channel stem (K = 27) is a direct fp32 convolution on
 the vector ALU fused with its PReLU (``mq_stem_conv3x3_f32``: writes the first block's input pair and its downsample's operand, never
 the full-resolution fp32 tensor); the head (bn2 - flatten - fc - features = one 7 x 7 "convolution", split-K) goes through
-``mq_im2col_split_f32`` + the encoder GEMM; ``MQ_ARCFACE_CONV=im2col`` runs
-EVERY convolution that way (round 4's first form).  The implicit kernel walks K as (32-channel block, tap) -- the nine taps of a block re-read the same
-input lines back to back, +6 % from L2 hits alone; with ``MQ_CONV_KORDER=tap`` it walks K like the explicit path and the two
-forwards agree bit for bit (tests/test_arcface_gpu.py), otherwise within fp32 rounding.
+``mq_im2col_split_f32`` + the encoder GEMM.  ``_forward_im2col`` runs EVERY convolution that way (round 4's first form, kept as the
+check of the implicit one).  The implicit kernel walks K as (32-channel block, tap) -- the nine taps of a block re-read the same
+input lines back to back, +6 % from L2 hits alone -- and the library picks its tile; the two forwards agree within fp32 rounding
+(tests/test_arcface_gpu.py; per convolution, the (tap, block) order of the explicit path gives its bits exactly).
 
 Parity: arcface_torch is not vendored by the reference and not installable here -- ``oracle/arcface.py`` restates the PUBLISHED
 definition (parity unpinned); ``tests/test_arcface_gpu.py`` holds this module to that oracle within 1e-3.
@@ -30,8 +30,9 @@ definition (parity unpinned); ``tests/test_arcface_gpu.py``
 ``v_mfma_f32_32x32x16_f16`` per 16 k instead of three bf16 products, and the rounding points are autocast's: the convolution's
 output is rounded BEFORE its BatchNorm, so nothing is folded -- each convolution keeps its fp16 weights and its BatchNorm as an
 affine of the epilogue (``mq_conv3x3_f16``, ``mq_stem_conv3x3_f16``, ``mq_conv1x1_f16``; ``mq_head_prep_f16`` hands bn2's fp16
-output to the unchanged fp32-class head GEMM).  tests/test_arcface_fp16_gpu.py pins each kernel against a torch restatement of
-those rounding points (tests/autocast_schedule.py)."""
+output to the unchanged fp32-class head GEMM).  Both precisions walk the blocks in one ``_forward``; only the stem, the 3 x 3
+launch, the downsample and the hand-off to the head differ, and a model holds the weights of its own precision only.
+tests/test_arcface_fp16_gpu.py pins each kernel against a torch restatement of those rounding points (tests/autocast_schedule.py)."""
 import os
 
 import numpy as np
@@ -43,6 +44,8 @@ from .encoders import EPI_BIAS, EPI_BIAS_RESIDUAL, SplitAct, _HipEncoder, _check
 EPS = 1e-5
 LAYERS = (3, 4, 14, 3)
 PRECISIONS = ("fp32", "fp16")
+CONV_TILE_AUTO, CONV_K_CHANNEL_MAJOR = 0, 0x100   # MQ_CONV_TILE_AUTO, MQ_CONV_K_CHANNEL_MAJOR (include/meerqat_hip.h)
+HEAD_SPLITS = 49   # workgroup rows of the head's split-K GEMM
 
 
 def _half(a):
@@ -73,18 +76,22 @@ def _np(x):
 
 
 class _Conv:
-    """One convolution as the GEMM sees it: W [Cout, Kpad] (kh, kw, cin order, the BatchNorm behind it folded in), bias [Cout]."""
+    """One convolution's geometry: Cout, Cin, k x k, stride, padding; the GEMM's K, (kh, kw, cin), padded to kpad, a multiple of 32."""
 
-    def __init__(self, weight, post_bn, k, stride, pad):
-        w = np.asarray(weight, np.float64)                       # [Cout, Cin, k, k]
-        a, b = post_bn
-        w2 = w.transpose(0, 2, 3, 1).reshape(w.shape[0], -1) * a[:, None]
-        self.k_true = w2.shape[1]
-        self.kpad = (self.k_true + 31) // 32 * 32
-        if self.kpad != self.k_true:
-            w2 = np.concatenate([w2, np.zeros((w2.shape[0], self.kpad - self.k_true))], axis=1)
-        self.w2, self.b = w2.astype(np.float32), b.astype(np.float32)
-        self.cout, self.cin, self.k, self.stride, self.pad = w.shape[0], w.shape[1], k, stride, pad
+    def __init__(self, weight, k, stride, pad):
+        self.cout, self.cin = weight.shape[:2]
+        self.k, self.stride, self.pad = k, stride, pad
+        self.kpad = (k * k * self.cin + 31) // 32 * 32
+
+
+def _folded(weight, post_bn, kpad):
+    """fp32 form of a convolution: W [Cout, kpad] ((kh, kw, cin) order, zeros beyond) with the BatchNorm behind it folded in, and the
+    bias [Cout]"""
+    w = np.asarray(weight, np.float64)                       # [Cout, Cin, k, k]
+    a, b = post_bn
+    w2 = w.transpose(0, 2, 3, 1).reshape(w.shape[0], -1) * a[:, None]
+    w2 = np.concatenate([w2, np.zeros((w2.shape[0], kpad - w2.shape[1]))], axis=1)
+    return w2.astype(np.float32), b.astype(np.float32)
 
 
 class ArcFaceR50(_HipEncoder):
@@ -103,22 +110,39 @@ class ArcFaceR50(_HipEncoder):
         # faces/s at 328 with the first implicit kernel; 23.8 k / 24.7 k at 328 / 656 with the final one)
         state = {k: _np(v).astype(np.float32) for k, v in state.items() if not k.endswith("num_batches_tracked")}
         self.layers, self.chunk = tuple(layers), int(chunk)
-        self._convs, self._vecs = {}, {}
-
-        def conv(name, post, k, stride, pad):
-            c = _Conv(state[name + ".weight"], _affine(state, post), k, stride, pad)
-            self._reg(name + ".w2", torch.from_numpy(c.w2))
-            self._reg(name + ".b", torch.from_numpy(c.b))
-            self._convs[name] = c
+        self._convs = {}
+        f16 = precision == "fp16"
 
         def vec(name, arr):
             self._reg(name, torch.from_numpy(np.ascontiguousarray(arr, np.float32)))
-            self._vecs[name] = name.replace(".", "_")
+
+        def prelu(name):  # fp16: autocast casts the slopes
+            w = state[name + ".weight"]
+            vec(name, _half(w) if f16 else w)
+
+        def conv(name, post, k, stride, pad):
+            """fp32: the BatchNorm ``post`` folded into the weights and a bias (w2, b).  fp16: nothing folded -- autocast rounds the
+            convolution's output before the BatchNorm reads it -- the weights rounded to fp16 (w16: tile layout for 3 x 3, row-major
+            [Cout, Cin] for 1 x 1) and the BatchNorm as (scale, shift) (ps, pb)."""
+            w = state[name + ".weight"]
+            c = self._convs[name] = _Conv(w, k, stride, pad)
+            if not f16:
+                w2, b = _folded(w, _affine(state, post), c.kpad)
+                self._reg(name + ".w2", torch.from_numpy(w2))
+                self._reg(name + ".b", torch.from_numpy(b))
+                return
+            a, b = _affine(state, post)
+            vec(name + ".ps", a)
+            vec(name + ".pb", b)
+            if name != "conv1":  # the stem's weights: conv1.wt
+                w16 = _f16_bits(w.transpose(0, 2, 3, 1).reshape(c.cout, -1))   # int16 bits as they are (_reg would convert to fp32)
+                self.register_buffer((name + ".w16").replace(".", "_"), (_tile(w16) if k == 3 else w16).contiguous(), persistent=False)
 
         conv("conv1", "bn1", 3, 1, 1)
-        vec("prelu", state["prelu.weight"])
-        # the stem as a direct convolution (mq_stem_conv3x3_f32): weights [27, 64], row (kh * 3 + kw) * 3 + c
-        self._reg("conv1.wt", torch.from_numpy(np.ascontiguousarray(self._convs["conv1"].w2[:, :27].T)))
+        prelu("prelu")
+        # the stem as a direct convolution (mq_stem_conv3x3_f32 / _f16): weights [27, 64], row (kh * 3 + kw) * 3 + c
+        wt = _half(state["conv1.weight"].transpose(2, 3, 1, 0).reshape(27, -1)) if f16 else self.conv1_w2[:, :27].T.numpy()
+        self._reg("conv1.wt", torch.from_numpy(np.ascontiguousarray(wt)))
         for s, n in enumerate(self.layers, start=1):
             for i in range(n):
                 p = f"layer{s}.{i}"
@@ -126,7 +150,7 @@ class ArcFaceR50(_HipEncoder):
                 vec(p + ".pre_scale", a)
                 vec(p + ".pre_shift", b)
                 conv(p + ".conv1", p + ".bn2", 3, 1, 1)
-                vec(p + ".prelu", state[p + ".prelu.weight"])
+                prelu(p + ".prelu")
                 conv(p + ".conv2", p + ".bn3", 3, 2 if i == 0 else 1, 1)
                 if i == 0:
                     conv(p + ".downsample.0", p + ".downsample.1", 1, 2, 0)
@@ -140,39 +164,6 @@ class ArcFaceR50(_HipEncoder):
         self._reg("fc.w2", torch.from_numpy((wfc * fa[:, None]).astype(np.float32)))
         self._reg("fc.b", torch.from_numpy((np.asarray(state["fc.bias"], np.float64) * fa + fb).astype(np.float32)))
         self.num_features = wfc.shape[0]
-        if precision == "fp16":
-            self._init_f16(state)
-
-    def _init_f16(self, state):
-        """fp16 mode: the UNFOLDED weights rounded to fp16 and, per convolution, the BatchNorm behind it as (scale, shift) -- autocast
-        rounds the convolution's output before the BatchNorm reads it; PReLU slopes rounded to fp16 (autocast casts them)."""
-        def raw(name, t):  # int16 bits as they are (_reg would convert to fp32)
-            self.register_buffer(name.replace(".", "_"), t.contiguous(), persistent=False)
-
-        def bn(name, post):
-            a, b = _affine(state, post)
-            self._reg(name + ".ps", torch.from_numpy(a.astype(np.float32)))
-            self._reg(name + ".pb", torch.from_numpy(b.astype(np.float32)))
-
-        def conv3x3(name, post):
-            w = np.asarray(state[name + ".weight"], np.float32)            # [Cout, Cin, 3, 3] -> [Cout, (kh, kw, cin)]
-            raw(name + ".w16", _tile(_f16_bits(w.transpose(0, 2, 3, 1).reshape(w.shape[0], -1))))
-            bn(name, post)
-
-        w = np.asarray(state["conv1.weight"], np.float32)                  # the stem: [27, 64], row (kh * 3 + kw) * 3 + c
-        self._reg("conv1.wt16", torch.from_numpy(np.ascontiguousarray(_half(w.transpose(2, 3, 1, 0).reshape(27, -1)))))
-        bn("conv1", "bn1")
-        self._reg("prelu16", torch.from_numpy(_half(state["prelu.weight"])))
-        for s, n in enumerate(self.layers, start=1):
-            for i in range(n):
-                p = f"layer{s}.{i}"
-                conv3x3(p + ".conv1", p + ".bn2")
-                self._reg(p + ".prelu16", torch.from_numpy(_half(state[p + ".prelu.weight"])))
-                conv3x3(p + ".conv2", p + ".bn3")
-                if i == 0:
-                    w = np.asarray(state[p + ".downsample.0.weight"], np.float32)
-                    raw(p + ".downsample.0.w16", _f16_bits(w.reshape(w.shape[0], -1)))   # row-major [Cout, Cin]
-                    bn(p + ".downsample.0", p + ".downsample.1")
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -187,26 +178,31 @@ class ArcFaceR50(_HipEncoder):
         return cls(state, **kw)
 
     # ------------------------------------------------------------------ forward
-    def _v(self, name):
-        return getattr(self, self._vecs[name]) if name is not None else None
+    def _b(self, name):
+        return getattr(self, name.replace(".", "_"))
+
+    def _zeros(self, dev):
+        zeros = self.__dict__.setdefault("_zero_pages", {})
+        if dev not in zeros:
+            zeros[dev] = torch.zeros(64, dtype=torch.uint8, device=dev)
+        return zeros[dev]
+
+    def _wsplit(self, name):
+        w = self._b(name)
+        cache = self.__dict__.setdefault("_split_cache", {})
+        key = (name, w.device, w.data_ptr())
+        if key not in cache:
+            cache[key] = split_bf16_tiled(w)
+        return cache[key]
 
     def _conv(self, name, x, B, H, W, nchw=False, slope=None, scale=None, shift=None, residual=None):
         """x: fp32 [B, H, W, Cin] (or NCHW) -> ([B * Ho * Wo, Cout] fp32, Ho, Wo)"""
         c = self._convs[name]
         Ho, Wo = (H + 2 * c.pad - c.k) // c.stride + 1, (W + 2 * c.pad - c.k) // c.stride + 1
         A = self._im2col(x, B, H, W, c.cin, nchw, c.k, c.k, c.stride, c.pad, c.kpad, slope, scale, shift)
-        y = gemm_nt(A, getattr(self, (name + ".w2").replace(".", "_")), bias=getattr(self, (name + ".b").replace(".", "_")),
-                    residual=residual, epilogue=EPI_BIAS_RESIDUAL if residual is not None else EPI_BIAS,
-                    wsplit=self._wsplit(name + ".w2"))
+        y = gemm_nt(A, self._b(name + ".w2"), bias=self._b(name + ".b"), residual=residual,
+                    epilogue=EPI_BIAS_RESIDUAL if residual is not None else EPI_BIAS, wsplit=self._wsplit(name + ".w2"))
         return y, Ho, Wo
-
-    def _wsplit(self, name):
-        w = getattr(self, name.replace(".", "_"))
-        cache = self.__dict__.setdefault("_split_cache", {})
-        key = (name, w.device, w.data_ptr())
-        if key not in cache:
-            cache[key] = split_bf16_tiled(w)
-        return cache[key]
 
     @staticmethod
     def _im2col(x, B, H, W, C, nchw, KH, KW, stride, pad, kpad, slope, scale, shift):
@@ -220,55 +216,94 @@ class ArcFaceR50(_HipEncoder):
                                                A.hi.data_ptr(), A.lo.data_ptr(), kpad, _stream(x)), "mq_im2col_split_f32")
         return A
 
-    def _conv3x3(self, name, xin, B, H, W, slope=None, residual=None, scale=None, shift=None, tile=0):
-        """The 3 x 3 convolution ``name`` as an implicit GEMM (mq_conv3x3_pair_f32) on ``xin``, the SplitAct [B * H * W, Cin] of its
-        input AFTER the pre-operations.  ``slope``: -> SplitAct of prelu(conv + bias).  Otherwise: -> (fp32 conv + bias + residual,
-        SplitAct of that * scale + shift or None)."""
+    def _stem(self, x, first):
+        """The stem fused with its PReLU: -> (block ``first``'s conv1 input, bn1 applied; the operand of its strided 1 x 1 downsample,
+        the activated pixels at even coordinates) -- the full-resolution tensor is never stored.  fp32: split pairs; fp16: fp16."""
         lib = _lib.load()
-        c = self._convs[name]
-        assert c.k == 3 and c.pad == 1 and xin.shape == (B * H * W, c.cin)
+        B, H, W, dev = x.shape[0], self.image_size, self.image_size, x.device
+        ptr = lambda n: self._b(n).data_ptr()  # noqa: E731
+        with torch.cuda.device(dev):
+            if self.precision == "fp16":
+                xin, ds_in = f16_empty(B * H * W, 64, dev), f16_empty(B * (H // 2) * (W // 2), 64, dev)
+                _lib.check(lib.mq_stem_conv3x3_f16(x.data_ptr(), B, H, W, ptr("conv1.wt"), ptr("conv1.ps"), ptr("conv1.pb"), ptr("prelu"),
+                                                   ptr(first + ".pre_scale"), ptr(first + ".pre_shift"), xin.data_ptr(), ds_in.data_ptr(),
+                                                   _stream(x)), "mq_stem_conv3x3_f16")
+            else:
+                xin, ds_in = SplitAct.empty(B * H * W, 64, dev), SplitAct.empty(B * (H // 2) * (W // 2), 64, dev)
+                _lib.check(lib.mq_stem_conv3x3_f32(x.data_ptr(), B, H, W, ptr("conv1.wt"), ptr("conv1.b"), ptr("prelu"),
+                                                   ptr(first + ".pre_scale"), ptr(first + ".pre_shift"), xin.hi.data_ptr(), xin.lo.data_ptr(),
+                                                   ds_in.hi.data_ptr(), ds_in.lo.data_ptr(), _stream(x)), "mq_stem_conv3x3_f32")
+        return xin, ds_in
+
+    def _conv3x3(self, name, xin, B, H, W, slope=None, residual=None, scale=None, shift=None):
+        """The 3 x 3 convolution ``name`` as an implicit GEMM on ``xin`` [B * H * W, Cin], its input AFTER the pre-operations (fp32: a
+        SplitAct, mq_conv3x3_pair_f32; fp16: one fp16 tensor, mq_conv3x3_f16).  ``slope``: -> P = prelu(conv).  Otherwise: -> (Y = conv
+        + residual, P = Y * scale + shift or None).  The library picks the tile; K is walked by channel block."""
+        lib = _lib.load()
+        c, f16 = self._convs[name], self.precision == "fp16"
+        assert c.k == 3 and c.pad == 1 and (f16 or xin.shape == (B * H * W, c.cin))
         Ho, Wo = (H - 1) // c.stride + 1, (W - 1) // c.stride + 1
         M, dev = B * Ho * Wo, xin.device
-        if (tile == 0 and c.stride == 1 and W <= 127 and str(c.cout) in os.environ.get("MQ_CONV_PATCH", "64").split(",")
-                and os.environ.get("MQ_CONV_KORDER", "channel") != "tap"):
-            tile = 5  # MQ_CONV_TILE_PATCH_256x64: few output channels -- the nine taps read one LDS-resident input patch
-        wh, wl = self._wsplit(name + ".w2")
-        bias = getattr(self, (name + ".b").replace(".", "_"))
-        zeros = self.__dict__.setdefault("_zero_pages", {})
-        if dev not in zeros:
-            zeros[dev] = torch.zeros(64, dtype=torch.uint8, device=dev)
-        P = SplitAct.empty(M, c.cout, dev) if (slope is not None or scale is not None) else None
-        Y = torch.empty((M, c.cout), dtype=torch.float32, device=dev) if slope is None else None
+        P = Y = None
+        if slope is not None or scale is not None:
+            P = f16_empty(M, c.cout, dev) if f16 else SplitAct.empty(M, c.cout, dev)
+        if slope is None:
+            Y = f16_empty(M, c.cout, dev) if f16 else torch.empty((M, c.cout), dtype=torch.float32, device=dev)
         p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        tile = CONV_TILE_AUTO | CONV_K_CHANNEL_MAJOR
         with torch.cuda.device(dev):
-            _lib.check(lib.mq_conv3x3_pair_f32(xin.hi.data_ptr(), xin.lo.data_ptr(), B, H, W, c.cin, c.stride, wh.data_ptr(), wl.data_ptr(),
-                                               c.cout, bias.data_ptr(), p(slope), p(residual), p(scale), p(shift), p(Y),
-                                               P.hi.data_ptr() if P is not None else None, P.lo.data_ptr() if P is not None else None,
-                                               zeros[dev].data_ptr(), int(tile) | (0 if os.environ.get("MQ_CONV_KORDER", "channel") == "tap" else 0x100),
-                                               _stream(xin.hi)), "mq_conv3x3_pair_f32")
+            if f16:
+                _lib.check(lib.mq_conv3x3_f16(xin.data_ptr(), B, H, W, c.cin, c.stride, self._b(name + ".w16").data_ptr(), c.cout,
+                                              self._b(name + ".ps").data_ptr(), self._b(name + ".pb").data_ptr(), p(slope), p(residual),
+                                              p(scale), p(shift), p(Y), p(P), self._zeros(dev).data_ptr(), tile, _stream(xin)),
+                           "mq_conv3x3_f16")
+            else:
+                wh, wl = self._wsplit(name + ".w2")
+                _lib.check(lib.mq_conv3x3_pair_f32(xin.hi.data_ptr(), xin.lo.data_ptr(), B, H, W, c.cin, c.stride, wh.data_ptr(),
+                                                   wl.data_ptr(), c.cout, self._b(name + ".b").data_ptr(), p(slope), p(residual), p(scale),
+                                                   p(shift), p(Y), P.hi.data_ptr() if P is not None else None,
+                                                   P.lo.data_ptr() if P is not None else None, self._zeros(dev).data_ptr(), tile,
+                                                   _stream(xin.hi)), "mq_conv3x3_pair_f32")
         return (P if slope is not None else (Y, P)), Ho, Wo
 
-    def _head(self, y, B, H, W):
-        """bn2 - flatten - fc - features: one 7 x 7 "convolution".  [B, 512] outputs over K = 25,088: as one GEMM two workgroups would
-        walk 784 K steps (1.65 ms of a 15-ms forward), so the K range is split over 49 workgroup rows and the fp32 partials summed
-        (mq_gemm_nt_bf16x3s_splitk_f32; MQ_ARCFACE_HEAD_SPLITS=1: the one-pass GEMM)."""
-        A = self._im2col(y, B, H, W, 512, False, H, W, 1, 0, H * W * 512, None, self._v("head.pre_scale"), self._v("head.pre_shift"))
-        return self._fc(A, y)
-
-    def _fc(self, A, y):
-        """fc - features on the split pair A [B, 25088] of bn2's output (y: any tensor on the device and stream)"""
-        nsplit = int(os.environ.get("MQ_ARCFACE_HEAD_SPLITS", "49"))
-        if nsplit <= 1:
-            return gemm_nt(A, self.fc_w2, bias=self.fc_b, epilogue=EPI_BIAS, wsplit=self._wsplit("fc.w2"))
+    def _downsample(self, name, src, B, H, W, stride):
+        """The 1 x 1 convolution ``name`` on ``src`` [B * H * W, Cin] at ``stride`` -> the block's shortcut [B * Ho * Wo, Cout] (fp32 /
+        fp16).  Stride 1: ``src`` is the stem's operand, already at even coordinates (fp32: as the GEMM's split pair)."""
+        if self.precision == "fp32":
+            if stride == 2:
+                return self._conv(name, src, B, H, W)[0]
+            return gemm_nt(src, self._b(name + ".w2"), bias=self._b(name + ".b"), epilogue=EPI_BIAS, wsplit=self._wsplit(name + ".w2"))
         lib = _lib.load()
+        c = self._convs[name]
+        y = f16_empty(B * ((H - 1) // stride + 1) * ((W - 1) // stride + 1), c.cout, src.device)
+        with torch.cuda.device(src.device):
+            _lib.check(lib.mq_conv1x1_f16(src.data_ptr(), B, H, W, c.cin, stride, self._b(name + ".w16").data_ptr(), c.cout,
+                                          self._b(name + ".ps").data_ptr(), self._b(name + ".pb").data_ptr(), y.data_ptr(), _stream(src)),
+                       "mq_conv1x1_f16")
+        return y
+
+    def _head(self, y, B, H, W):
+        """bn2 - flatten - fc - features: one 7 x 7 "convolution" on the last block's output ``y``.  bn2's output goes to the GEMM as a
+        split pair (fp32: mq_im2col_split_f32; fp16: mq_head_prep_f16, exact).  [B, 512] outputs over K = 25,088: as one GEMM two
+        workgroups would walk 784 K steps (1.65 ms of a 15-ms forward), so the K range is split over 49 workgroup rows and the fp32
+        partials summed (mq_gemm_nt_bf16x3s_splitk_f32)."""
+        lib = _lib.load()
+        dev = y.device
+        if self.precision == "fp16":
+            A = SplitAct.empty(B, H * W * 512, dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.mq_head_prep_f16(y.data_ptr(), B, H * W, 512, self._b("head.pre_scale").data_ptr(),
+                                                self._b("head.pre_shift").data_ptr(), A.hi.data_ptr(), A.lo.data_ptr(), _stream(y)),
+                           "mq_head_prep_f16")
+        else:
+            A = self._im2col(y, B, H, W, 512, False, H, W, 1, 0, H * W * 512, None, self._b("head.pre_scale"), self._b("head.pre_shift"))
         wh, wl = self._wsplit("fc.w2")
-        M, K = A.shape
-        N = self.fc_w2.shape[0]
-        out = torch.empty((M, N), dtype=torch.float32, device=y.device)
-        part = torch.empty((nsplit, M, N), dtype=torch.float32, device=y.device)
-        with torch.cuda.device(y.device):
+        K, N = H * W * 512, self.fc_w2.shape[0]
+        out = torch.empty((B, N), dtype=torch.float32, device=dev)
+        part = torch.empty((HEAD_SPLITS, B, N), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
             _lib.check(lib.mq_gemm_nt_bf16x3s_splitk_f32(A.hi.data_ptr(), A.lo.data_ptr(), wh.data_ptr(), wl.data_ptr(), self.fc_b.data_ptr(),
-                                                         out.data_ptr(), M, N, K, 1, nsplit, part.data_ptr(), _stream(y)),
+                                                         out.data_ptr(), B, N, K, 1, HEAD_SPLITS, part.data_ptr(), _stream(y)),
                        "mq_gemm_nt_bf16x3s_splitk_f32")
         return out
 
@@ -282,121 +317,41 @@ class ArcFaceR50(_HipEncoder):
         return self._forward(x)
 
     def _forward(self, x):
-        if self.precision == "fp16":
-            return self._forward_f16(x)
-        if os.environ.get("MQ_ARCFACE_CONV", "implicit") == "im2col":
-            return self._forward_im2col(x)
+        """The IResNet walk for both precisions: an IBasicBlock is conv1 (epilogue: PReLU) and conv2 (epilogue: the shortcut, the next
+        block's bn1), with the strided 1 x 1 downsample of a stage's first block in between."""
         B, H, W = x.shape[0], self.image_size, self.image_size
         blocks = [f"layer{s}.{i}" for s, n in enumerate(self.layers, start=1) for i in range(n)]
-        # stem: direct fp32 convolution fused with its PReLU; writes the first block's conv1 input pair (bn1 applied) and the A operand
-        # of its strided 1 x 1 downsample (the activated pixels at even coordinates) -- the full-resolution fp32 tensor is never stored
-        lib = _lib.load()
-        xin = SplitAct.empty(B * H * W, 64, x.device)
+        xin, ds_in = self._stem(x, blocks[0])
         y = None
-        ds_in = SplitAct.empty(B * (H // 2) * (W // 2), 64, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.mq_stem_conv3x3_f32(x.data_ptr(), B, H, W, self.conv1_wt.data_ptr(), self.conv1_b.data_ptr(), self._v("prelu").data_ptr(),
-                                               self._v(blocks[0] + ".pre_scale").data_ptr(), self._v(blocks[0] + ".pre_shift").data_ptr(),
-                                               xin.hi.data_ptr(), xin.lo.data_ptr(), ds_in.hi.data_ptr(), ds_in.lo.data_ptr(), _stream(x)),
-                       "mq_stem_conv3x3_f32")
         for bi, p in enumerate(blocks):
             nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
-            o1, _, _ = self._conv3x3(p + ".conv1", xin, B, H, W, slope=self._v(p + ".prelu"))
-            if (p + ".downsample.0") in self._convs:
-                if ds_in is not None:   # the first block: the stem wrote the 1 x 1 stride-2 "patches"
-                    name = p + ".downsample.0"
-                    identity = gemm_nt(ds_in, getattr(self, (name + ".w2").replace(".", "_")), bias=getattr(self, (name + ".b").replace(".", "_")),
-                                       epilogue=EPI_BIAS, wsplit=self._wsplit(name + ".w2"))
-                    ds_in = None
-                else:
-                    identity, _, _ = self._conv(p + ".downsample.0", y, B, H, W)
+            o1, _, _ = self._conv3x3(p + ".conv1", xin, B, H, W, slope=self._b(p + ".prelu"))
+            if ds_in is not None:   # the first block: the stem wrote the 1 x 1 stride-2 "patches"
+                identity, ds_in = self._downsample(p + ".downsample.0", ds_in, B, H // 2, W // 2, 1), None
+            elif (p + ".downsample.0") in self._convs:
+                identity = self._downsample(p + ".downsample.0", y, B, H, W, 2)
             else:
                 identity = y
             (y, xin), H, W = self._conv3x3(p + ".conv2", o1, B, H, W, residual=identity,
-                                           scale=self._v(nxt + ".pre_scale") if nxt else None,
-                                           shift=self._v(nxt + ".pre_shift") if nxt else None)
+                                           scale=self._b(nxt + ".pre_scale") if nxt else None,
+                                           shift=self._b(nxt + ".pre_shift") if nxt else None)
         return self._head(y, B, H, W)
 
     def _forward_im2col(self, x):
-        """Round 4's first form, kept as the check of the implicit one (MQ_ARCFACE_CONV=im2col): every convolution an explicit
-        im2col + GEMM.  Same products in the same order: the two forwards agree bit for bit."""
+        """Round 4's first form of the fp32 forward, kept as the check of the implicit one: every convolution an explicit im2col + GEMM."""
         B, H, W = x.shape[0], self.image_size, self.image_size
         # stem: conv - BN (folded); its PReLU is applied where the result is read (the first block's im2cols)
         y, H, W = self._conv("conv1", x, B, H, W, nchw=True)
-        pending = self._v("prelu")
+        pending = self._b("prelu")
         for s, n in enumerate(self.layers, start=1):
             for i in range(n):
                 p = f"layer{s}.{i}"
-                o1, _, _ = self._conv(p + ".conv1", y, B, H, W, slope=pending, scale=self._v(p + ".pre_scale"), shift=self._v(p + ".pre_shift"))
+                o1, _, _ = self._conv(p + ".conv1", y, B, H, W, slope=pending, scale=self._b(p + ".pre_scale"), shift=self._b(p + ".pre_shift"))
                 if i == 0:
                     identity, Ho, Wo = self._conv(p + ".downsample.0", y, B, H, W, slope=pending)
                 else:
                     assert pending is None
                     identity = y
-                y, Ho, Wo = self._conv(p + ".conv2", o1, B, H, W, slope=self._v(p + ".prelu"), residual=identity)
+                y, Ho, Wo = self._conv(p + ".conv2", o1, B, H, W, slope=self._b(p + ".prelu"), residual=identity)
                 H, W, pending = Ho, Wo, None
         return self._head(y, B, H, W)
-
-    # ------------------------------------------------------------------ fp16 (the reference's autocast precision)
-    def _b(self, name):
-        return getattr(self, name.replace(".", "_"))
-
-    def _zeros(self, dev):
-        zeros = self.__dict__.setdefault("_zero_pages", {})
-        if dev not in zeros:
-            zeros[dev] = torch.zeros(64, dtype=torch.uint8, device=dev)
-        return zeros[dev]
-
-    def _conv3x3_f16(self, name, xin, B, H, W, slope=None, residual=None, scale=None, shift=None, tile=0):
-        """mq_conv3x3_f16 of ``name`` on the fp16 activation ``xin`` [B * H * W, Cin].  ``slope``: -> P = r(prelu(t)).  Otherwise:
-        -> (Y = r(t + residual), P = r(Y * scale + shift) or None)."""
-        lib = _lib.load()
-        c = self._convs[name]
-        Ho, Wo = (H - 1) // c.stride + 1, (W - 1) // c.stride + 1
-        M, dev = B * Ho * Wo, xin.device
-        P = f16_empty(M, c.cout, dev) if (slope is not None or scale is not None) else None
-        Y = f16_empty(M, c.cout, dev) if slope is None else None
-        p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        with torch.cuda.device(dev):
-            _lib.check(lib.mq_conv3x3_f16(xin.data_ptr(), B, H, W, c.cin, c.stride, self._b(name + ".w16").data_ptr(), c.cout,
-                                          self._b(name + ".ps").data_ptr(), self._b(name + ".pb").data_ptr(), p(slope), p(residual),
-                                          p(scale), p(shift), p(Y), p(P), self._zeros(dev).data_ptr(), int(tile) | 0x100, _stream(xin)),
-                       "mq_conv3x3_f16")
-        return (P if slope is not None else (Y, P)), Ho, Wo
-
-    def _forward_f16(self, x):
-        """The trunk at autocast's rounding points, one fp16 tensor per activation; the head fp32-class on bn2's fp16 output."""
-        lib = _lib.load()
-        B, H, W, dev = x.shape[0], self.image_size, self.image_size, x.device
-        blocks = [f"layer{s}.{i}" for s, n in enumerate(self.layers, start=1) for i in range(n)]
-        xin, ds_in = f16_empty(B * H * W, 64, dev), f16_empty(B * (H // 2) * (W // 2), 64, dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mq_stem_conv3x3_f16(x.data_ptr(), B, H, W, self.conv1_wt16.data_ptr(), self.conv1_ps.data_ptr(),
-                                               self.conv1_pb.data_ptr(), self.prelu16.data_ptr(), self._v(blocks[0] + ".pre_scale").data_ptr(),
-                                               self._v(blocks[0] + ".pre_shift").data_ptr(), xin.data_ptr(), ds_in.data_ptr(), _stream(x)),
-                       "mq_stem_conv3x3_f16")
-        y = None
-        for bi, p in enumerate(blocks):
-            nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
-            o1, _, _ = self._conv3x3_f16(p + ".conv1", xin, B, H, W, slope=self._b(p + ".prelu16"))
-            if (p + ".downsample.0") in self._convs:
-                # the first block reads the stem's activation at even coordinates (stride 1 on D); later stages stride over y
-                src, h, w, stride = (ds_in, H // 2, W // 2, 1) if ds_in is not None else (y, H, W, 2)
-                name, c = p + ".downsample.0", self._convs[p + ".downsample.0"]
-                identity = f16_empty(B * ((h - 1) // stride + 1) * ((w - 1) // stride + 1), c.cout, dev)
-                with torch.cuda.device(dev):
-                    _lib.check(lib.mq_conv1x1_f16(src.data_ptr(), B, h, w, c.cin, stride, self._b(name + ".w16").data_ptr(), c.cout,
-                                                  self._b(name + ".ps").data_ptr(), self._b(name + ".pb").data_ptr(), identity.data_ptr(),
-                                                  _stream(x)), "mq_conv1x1_f16")
-                ds_in = None
-            else:
-                identity = y
-            (y, xin), H, W = self._conv3x3_f16(p + ".conv2", o1, B, H, W, residual=identity,
-                                               scale=self._v(nxt + ".pre_scale") if nxt else None,
-                                               shift=self._v(nxt + ".pre_shift") if nxt else None)
-        A = SplitAct.empty(B, H * W * 512, dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.mq_head_prep_f16(y.data_ptr(), B, H * W, 512, self._v("head.pre_scale").data_ptr(),
-                                            self._v("head.pre_shift").data_ptr(), A.hi.data_ptr(), A.lo.data_ptr(), _stream(x)),
-                       "mq_head_prep_f16")
-        return self._fc(A, x)

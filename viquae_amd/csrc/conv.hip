@@ -667,6 +667,37 @@ int launch_conv3x3_variant(const ConvArgs& a, int variant, hipStream_t st) {
     return MQ_EINVAL;
 }
 
+// The host side of mq_conv3x3_pair_f32 and mq_conv3x3_f16: `a` holds the caller's pointers (`operands`: its input, weight and
+// bias / BatchNorm pointers are all given); checks the shapes and the epilogue's outputs, fills in the geometry and the K order,
+// resolves MQ_CONV_TILE_AUTO and launches.
+template <bool F16>
+int run_conv3x3(ConvArgs a, bool operands, int B, int H, int W, int C, int stride, int N, int tile, hipStream_t st) {
+    if (B == 0) return MQ_OK;
+    if (!operands || !a.zeros || B < 0 || H <= 0 || W <= 0) return MQ_EINVAL;
+    if (C <= 0 || C % 32 || N <= 0 || N % 64 || (stride != 1 && stride != 2)) return MQ_EINVAL;
+    const bool prelu = a.slope != nullptr, pair = a.Ph && (F16 || a.Pl);
+    const bool res = F16 ? a.R16 != nullptr : a.R != nullptr, y = F16 ? a.Y16 != nullptr : a.Y != nullptr;
+    if (prelu && (res || y || a.scale || a.shift || !pair)) return MQ_EINVAL;  // EP_PRELU_PAIR
+    if (!prelu && (!res || !y)) return MQ_EINVAL;                               // EP_RESIDUAL_AFFINE
+    if ((a.scale == nullptr) != (a.shift == nullptr)) return MQ_EINVAL;
+    if (!prelu && a.scale && !pair) return MQ_EINVAL;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const size_t M = (size_t)B * Ho * Wo, P = (size_t)B * H * W;
+    if (M >= 0x7FFFFFFFull || P >= 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
+    a.H = H; a.W = W; a.C = C; a.N = N; a.stride = stride; a.Ho = Ho; a.Wo = Wo; a.M = (int)M;
+    a.cmajor = (tile & MQ_CONV_K_CHANNEL_MAJOR) ? 1 : 0;
+    tile &= ~MQ_CONV_K_CHANNEL_MAJOR;
+    if (tile == MQ_CONV_TILE_AUTO) {
+        // the 64-channel stage reads one LDS-resident patch per channel block; wider stages: the widest tile the channel count fills
+        // while it still gives every CU a workgroup
+        if (N == 64 && stride == 1 && a.cmajor && 2 * W + 2 <= PT_PR - PT_MT) tile = MQ_CONV_TILE_PATCH_256x64;
+        else if (N % 256 == 0 && ((M + 255) / 256) * (size_t)(N / 256) >= 192) tile = MQ_CONV_TILE_256x256;
+        else if (N % 128 == 0) tile = ((M + 511) / 512) * (size_t)(N / 128) >= 192 ? MQ_CONV_TILE_512x128 : MQ_CONV_TILE_256x128;
+        else tile = MQ_CONV_TILE_512x64;
+    }
+    return prelu ? launch_conv3x3_variant<EP_PRELU_PAIR, F16>(a, tile, st) : launch_conv3x3_variant<EP_RESIDUAL_AFFINE, F16>(a, tile, st);
+}
+
 // ---- the stem: 3 -> 64 channels, 3 x 3, stride 1, padding 1 (K = 27: no matrix-pipe shape) -- direct fp32 convolution on the vector ALU.
 // Through im2col + GEMM + the elementwise pass that makes the first block's input pair, the stem moved 4.2 GB per 328 faces for 43
 // MFLOP per face (1.46 ms of a 15-ms forward); here the NCHW pixels are read once and only what the network reads next is written:
@@ -973,31 +1004,10 @@ int mq_conv3x3_pair_f32(const uint16_t* Xh_dev, const uint16_t* Xl_dev, int B, i
                         const uint16_t* Wl_dev, int N, const float* bias_dev, const float* prelu_slope_dev, const float* residual_dev,
                         const float* scale_dev, const float* shift_dev, float* Y_dev, uint16_t* Ph_dev, uint16_t* Pl_dev,
                         const void* zeros_dev, int tile, void* stream) {
-    if (B == 0) return MQ_OK;
-    if (!Xh_dev || !Xl_dev || !Wh_dev || !Wl_dev || !bias_dev || !zeros_dev || B < 0 || H <= 0 || W <= 0) return MQ_EINVAL;
-    if (C <= 0 || C % 32 || N <= 0 || N % 64 || (stride != 1 && stride != 2)) return MQ_EINVAL;
-    const bool prelu = prelu_slope_dev != nullptr;
-    if (prelu && (residual_dev || Y_dev || scale_dev || shift_dev || !Ph_dev || !Pl_dev)) return MQ_EINVAL;  // EP_PRELU_PAIR
-    if (!prelu && (!residual_dev || !Y_dev)) return MQ_EINVAL;                                               // EP_RESIDUAL_AFFINE
-    if ((scale_dev == nullptr) != (shift_dev == nullptr)) return MQ_EINVAL;
-    if (!prelu && scale_dev && (!Ph_dev || !Pl_dev)) return MQ_EINVAL;
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    const size_t M = (size_t)B * Ho * Wo, P = (size_t)B * H * W;
-    if (M >= 0x7FFFFFFFull || P >= 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
-    ConvArgs a;
+    ConvArgs a = {};
     a.Xh = Xh_dev; a.Xl = Xl_dev; a.Wh = Wh_dev; a.Wl = Wl_dev; a.bias = bias_dev; a.slope = prelu_slope_dev; a.R = residual_dev;
     a.scale = scale_dev; a.shift = shift_dev; a.Y = Y_dev; a.Ph = Ph_dev; a.Pl = Pl_dev; a.zeros = zeros_dev;
-    a.H = H; a.W = W; a.C = C; a.N = N; a.stride = stride; a.Ho = Ho; a.Wo = Wo; a.M = (int)M; a.ntm = a.ntn = 0;
-    a.cmajor = (tile & MQ_CONV_K_CHANNEL_MAJOR) ? 1 : 0;
-    tile &= ~MQ_CONV_K_CHANNEL_MAJOR;
-    if (tile == MQ_CONV_TILE_AUTO) {
-        // the widest tile the channel count fills; a 256-column tile only while it still gives every CU a workgroup
-        if (N % 256 == 0 && ((M + 255) / 256) * (size_t)(N / 256) >= 192) tile = MQ_CONV_TILE_256x256;
-        else if (N % 128 == 0) tile = ((M + 511) / 512) * (size_t)(N / 128) >= 192 ? MQ_CONV_TILE_512x128 : MQ_CONV_TILE_256x128;
-        else tile = MQ_CONV_TILE_512x64;
-    }
-    return prelu ? launch_conv3x3_variant<EP_PRELU_PAIR>(a, tile, (hipStream_t)stream)
-                 : launch_conv3x3_variant<EP_RESIDUAL_AFFINE>(a, tile, (hipStream_t)stream);
+    return run_conv3x3<false>(a, Xh_dev && Xl_dev && Wh_dev && Wl_dev && bias_dev, B, H, W, C, stride, N, tile, (hipStream_t)stream);
 }
 
 int mq_stem_conv3x3_f32(const float* x_dev, int B, int H, int W, const float* wt_dev, const float* bias_dev, const float* prelu_slope_dev,
@@ -1018,33 +1028,10 @@ int mq_stem_conv3x3_f32(const float* x_dev, int B, int H, int W, const float* wt
 int mq_conv3x3_f16(const uint16_t* X_dev, int B, int H, int W, int C, int stride, const uint16_t* Wt_dev, int N, const float* post_scale_dev,
                    const float* post_shift_dev, const float* prelu_slope_dev, const uint16_t* residual_dev, const float* scale_dev,
                    const float* shift_dev, uint16_t* Y_dev, uint16_t* P_dev, const void* zeros_dev, int tile, void* stream) {
-    if (B == 0) return MQ_OK;
-    if (!X_dev || !Wt_dev || !post_scale_dev || !post_shift_dev || !zeros_dev || B < 0 || H <= 0 || W <= 0) return MQ_EINVAL;
-    if (C <= 0 || C % 32 || N <= 0 || N % 64 || (stride != 1 && stride != 2)) return MQ_EINVAL;
-    const bool prelu = prelu_slope_dev != nullptr;
-    if (prelu && (residual_dev || Y_dev || scale_dev || shift_dev || !P_dev)) return MQ_EINVAL;  // EP_PRELU_PAIR
-    if (!prelu && (!residual_dev || !Y_dev)) return MQ_EINVAL;                                   // EP_RESIDUAL_AFFINE
-    if ((scale_dev == nullptr) != (shift_dev == nullptr)) return MQ_EINVAL;
-    if (!prelu && scale_dev && !P_dev) return MQ_EINVAL;
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    const size_t M = (size_t)B * Ho * Wo, P = (size_t)B * H * W;
-    if (M >= 0x7FFFFFFFull || P >= 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
     ConvArgs a = {};
     a.Xh = X_dev; a.Wh = Wt_dev; a.slope = prelu_slope_dev; a.scale = scale_dev; a.shift = shift_dev; a.Ph = P_dev; a.zeros = zeros_dev;
     a.pscale = post_scale_dev; a.pshift = post_shift_dev; a.R16 = residual_dev; a.Y16 = Y_dev;
-    a.H = H; a.W = W; a.C = C; a.N = N; a.stride = stride; a.Ho = Ho; a.Wo = Wo; a.M = (int)M;
-    a.cmajor = (tile & MQ_CONV_K_CHANNEL_MAJOR) ? 1 : 0;
-    tile &= ~MQ_CONV_K_CHANNEL_MAJOR;
-    if (tile == MQ_CONV_TILE_AUTO) {
-        // the 64-channel stage reads one LDS-resident patch per channel block; wider stages: the widest tile the channel count fills
-        // while it still gives every CU a workgroup
-        if (N == 64 && stride == 1 && a.cmajor && 2 * W + 2 <= PT_PR - PT_MT) tile = MQ_CONV_TILE_PATCH_256x64;
-        else if (N % 256 == 0 && ((M + 255) / 256) * (size_t)(N / 256) >= 192) tile = MQ_CONV_TILE_256x256;
-        else if (N % 128 == 0) tile = ((M + 511) / 512) * (size_t)(N / 128) >= 192 ? MQ_CONV_TILE_512x128 : MQ_CONV_TILE_256x128;
-        else tile = MQ_CONV_TILE_512x64;
-    }
-    return prelu ? launch_conv3x3_variant<EP_PRELU_PAIR, true>(a, tile, (hipStream_t)stream)
-                 : launch_conv3x3_variant<EP_RESIDUAL_AFFINE, true>(a, tile, (hipStream_t)stream);
+    return run_conv3x3<true>(a, X_dev && Wt_dev && post_scale_dev && post_shift_dev, B, H, W, C, stride, N, tile, (hipStream_t)stream);
 }
 
 int mq_stem_conv3x3_f16(const float* x_dev, int B, int H, int W, const float* wt_dev, const float* post_scale_dev, const float* post_shift_dev,
