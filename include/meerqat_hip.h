@@ -673,6 +673,27 @@ int mq_warp_affine_faces_f32(const uint8_t *images_dev, const int64_t *offsets_d
                              const int32_t *face_image_dev, const double *minv_dev, int nfaces, int size, float *out_dev,
                              void *stream);
 
+/* ---- reader: MultiPassageBERT answer extraction (csrc/reader.hip; the evaluation path of meerqat/train/trainee.py:742-824) ----
+ * N questions, M passages each, L tokens per (question, passage) pair; every array is dense fp32 / int64, row-major.
+ * mq_reader_qa_head_f32: BertForQuestionAnswering.qa_outputs on the last hidden states h [rows, H] (H a multiple of 4; h and w
+ *   16-byte aligned): start[r] = h[r] . w[0] + b[0], end[r] = h[r] . w[1] + b[1] for w [2, H], b [2] (NULL = no bias), fp32
+ *   fused multiply-adds.  One wave per row, the rows spread over the whole GPU.
+ * mq_reader_log_softmax_f32: nn.LogSoftmax over each question's M * L positions (meerqat/train/optim.py:42-87), for the start
+ *   and the end logits [N, M, L]: logp = fl(fl(x - max) - logf(S)) with S = sum expf(x - max) summed in fp32 as per-thread
+ *   partials and a tree; p = expf(logp).  Writes the four [N, M, L] arrays.
+ * mq_reader_best_spans_f32: get_best_spans (meerqat/models/qa.py:18-77) on probabilities [N, M, L]: candidate P[m, i, j] =
+ *   fl(s_i e_j) for i <= j, else 0; row i = 0 zeroed when cannot_be_first_token; times weights[q, m] when weights_dev [N, M] is
+ *   given (shifted to >= 1 by the caller, as the reference does in place).  Per question: the lowest passage holding the
+ *   largest candidate, then the lowest flat index i * L + j reaching it -> passage, start = i, end = j + 1 (exclusive), int64 [N].
+ *   Bit-exact for finite non-negative inputs (no denormal flushing).  M * L * L must stay below 2^32 (MQ_EINVAL). */
+int mq_reader_qa_head_f32(const float *h_dev, const float *w_dev, const float *b_dev, float *start_dev, float *end_dev,
+                          int64_t rows, int H, void *stream);
+int mq_reader_log_softmax_f32(const float *start_logits_dev, const float *end_logits_dev, int N, int M, int L,
+                              float *start_logp_dev, float *end_logp_dev, float *start_p_dev, float *end_p_dev, void *stream);
+int mq_reader_best_spans_f32(const float *start_p_dev, const float *end_p_dev, const float *weights_dev, int N, int M, int L,
+                             int cannot_be_first_token, int64_t *passage_dev, int64_t *start_dev, int64_t *end_dev,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,3 +181,13 @@ def import_reference_embedding():
         warnings.simplefilter("ignore")
         import meerqat.ir.embedding as ref_embedding
     return ref_embedding
+
+
+def install_reader_stubs():
+    """install_stubs() plus an inert pytorch_lightning, so that meerqat.train.data / meerqat.train.trainee import: the reader
+    golden (tools/make_golden_reader.py) calls their evaluation functions through stand-in objects, never Lightning itself."""
+    install_stubs()
+    if "pytorch_lightning" not in sys.modules:
+        _module("pytorch_lightning", LightningDataModule=type("LightningDataModule", (), {}),
+                LightningModule=type("LightningModule", (), {}))
+        _module("pytorch_lightning.utilities")

@@ -103,6 +103,9 @@ SIGNATURES = {
     "mq_fuse_fit_wsum_f64": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int,
                                      c_int, c_ptr, c_ptr, c_ptr, c_sz, c_ptr]),
     "mq_format_run_json": (c_i64, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr]),
+    "mq_reader_qa_head_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr]),
+    "mq_reader_log_softmax_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mq_reader_best_spans_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 

@@ -8,7 +8,9 @@ Class names are resolved in :mod:`viquae_amd.encoders` FIRST (``DPRContextEncode
 :class:`viquae_amd.image.preprocess.CLIPImageProcessorHIP`, so the reference's JSON configs
 (experiments/ir/viquae/dpr/passages/config.json, experiments/image_embedding/clip/vit_config.json)
 load unchanged.  The reference also searches its own ``mm``/``qa``/``rr`` modules (multimodal
-encoders, readers, rerankers): those are outside this build."""
+encoders, readers, rerankers): of its readers, ``MultiPassageBERT`` (experiments/rc/viquae/config.yaml)
+resolves to the HIP-backed module, evaluated by :mod:`viquae_amd.rc.reader`; the multimodal readers
+and the rerankers are outside this build."""
 import os
 import warnings
 from pathlib import Path

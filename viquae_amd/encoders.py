@@ -1040,8 +1040,72 @@ class IntermediateLinearFusion(_MMEmbeddings):
         return ModelOutput(pooler_output=layernorm(out, self.ln_g, self.ln_b, mmc.layer_norm_eps, out=out))
 
 
+# --------------------------------------------------------------------------------------------------
+# reader
+# --------------------------------------------------------------------------------------------------
+def qa_head(h, w, b):
+    """BertForQuestionAnswering.qa_outputs on h [rows, H] (w [2, H], b [2]) -> logits [2, rows]: row 0 the start logits, row 1
+    the end logits (csrc/reader.hip, one wave per token row over the whole GPU)."""
+    _check_cuda(h, w)
+    lib = _lib.load()
+    h = h.contiguous()
+    rows, H = h.shape
+    out = torch.empty((2, rows), dtype=torch.float32, device=h.device)
+    with torch.cuda.device(h.device):
+        _lib.check(lib.mq_reader_qa_head_f32(h.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, out[0].data_ptr(),
+                                             out[1].data_ptr(), rows, H, _stream(h)), "mq_reader_qa_head_f32")
+    return out
+
+
+class MultiPassageBERT(_HipEncoder):
+    """meerqat.models.qa.MultiPassageBERT (a BertForQuestionAnswering; experiments/rc/viquae/config.yaml) in evaluation:
+    ``forward`` returns the start and end logits [B, L] of every position, padding and question tokens included -- the
+    reader's normalisation and span search (viquae_amd/rc/reader.py) see all of them, so the DENSE forward runs here (the
+    packed one drops the padding rows).  Reads ``BertForQuestionAnswering`` / ``MultiPassageBERT.save_pretrained`` checkpoints:
+    ``bert.*`` plus ``qa_outputs.weight`` / ``qa_outputs.bias``."""
+    config_class = dict
+
+    def __init__(self, config, state, fuse_ir_score=False):
+        super().__init__()
+        if fuse_ir_score or "score_proj_w" in state:
+            raise NotImplementedError("MultiPassageBERT fuse_ir_score (fusing the retrieval score into the logits) is not "
+                                      "provided: the shipped reader config sets fuse_ir_score: false")
+        self.config = dict(config)
+        if int(self.config.get("num_labels", 2)) != 2:
+            raise NotImplementedError("a question-answering head has two labels (start, end)")
+        self.bert = BertEncoderHIP(self.config, state, "bert.")
+        w = self._reg("qa_w", state["qa_outputs.weight"])
+        self._reg("qa_b", state["qa_outputs.bias"])
+        if tuple(w.shape) != (2, self.bert.hidden):
+            raise ValueError(f"qa_outputs.weight of shape {tuple(w.shape)}, expected (2, {self.bert.hidden})")
+        self.fuse_ir_score = False
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, fuse_ir_score=False, **kwargs):
+        """The checkpoint as saved; ``fuse_ir_score`` is the reader's only model option (false in the shipped config).  Any
+        other keyword (a Hugging Face ``config`` override, a dtype, ...) is refused rather than ignored."""
+        if kwargs:
+            raise NotImplementedError(f"MultiPassageBERT.from_pretrained: model_kwargs {sorted(kwargs)} are not supported "
+                                      "(the checkpoint is loaded as saved; only fuse_ir_score: false is accepted)")
+        config, state = read_checkpoint(pretrained_model_name_or_path)
+        return cls(config, state, fuse_ir_score=fuse_ir_score)
+
+    @classmethod
+    def from_state_dict(cls, config, state, fuse_ir_score=False):
+        return cls(config, state, fuse_ir_score=fuse_ir_score)
+
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, **unused):
+        """-> ModelOutput(start_logits [B, L], end_logits [B, L]) on the device"""
+        B, L = input_ids.shape
+        last, _ = self.bert(input_ids, token_type_ids, attention_mask)
+        logits = qa_head(last.view(B * L, -1), self.qa_w, self.qa_b).view(2, B, L)
+        return ModelOutput(start_logits=logits[0], end_logits=logits[1])
+
+
 HIP_CLASSES = {"DPRContextEncoder": DPRContextEncoder, "DPRQuestionEncoder": DPRQuestionEncoder, "CLIPModel": CLIPModel,
-               "ECAEncoder": ECAEncoder, "IntermediateLinearFusion": IntermediateLinearFusion}
+               "ECAEncoder": ECAEncoder, "IntermediateLinearFusion": IntermediateLinearFusion,
+               "MultiPassageBERT": MultiPassageBERT}
 
 
 def __getattr__(name):
