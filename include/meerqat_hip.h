@@ -508,6 +508,9 @@ int64_t mq_format_run_json(const char *qid_json, const int64_t *qid_off, int64_t
  * image height, coefficient ints, largest image width}.
  *   resize_mode  MQ_IMAGE_RESIZE_NONE | _SHORTEST (shortest edge -> size_h, long edge int(size_h * long / short), the
  *                `get_resize_output_image_size(default_to_square=False)` rule) | _EXACT (size_h x size_w)
+ *                OR MQ_IMAGE_CROP_TORCHVISION into it for torchvision's CenterCrop origin, int(round((size - crop) / 2.0)) with
+ *                Python's round-half-to-even, instead of the default (size - crop) / 2 rounded down (transformers' center_crop):
+ *                the two differ when size - crop = 3 (mod 4)
  *   MQ_EUNSUPPORTED when a resized image is smaller than the crop window (HF zero-pads; not provided) or for filters
  *   other than bilinear / bicubic.
  * mq_image_preprocess_u8: src_dev = the packed source buffer, geom_dev = geom_host copied to the device,
@@ -521,6 +524,7 @@ int64_t mq_format_run_json(const char *qid_json, const int64_t *qid_off, int64_t
 #define MQ_IMAGE_RESIZE_NONE 0
 #define MQ_IMAGE_RESIZE_SHORTEST 1
 #define MQ_IMAGE_RESIZE_EXACT 2
+#define MQ_IMAGE_CROP_TORCHVISION 0x100
 #define MQ_IMAGE_RESCALE 1
 #define MQ_IMAGE_NORMALIZE 2
 int mq_image_plan(const int64_t *sizes_host, int n_images, int resize_mode, int size_h, int size_w, int crop_h, int crop_w,
@@ -672,6 +676,32 @@ int mq_head_prep_f16(const uint16_t *X_dev, int B, int HW, int C, const float *s
 int mq_warp_affine_faces_f32(const uint8_t *images_dev, const int64_t *offsets_dev, const int32_t *hw_dev,
                              const int32_t *face_image_dev, const double *minv_dev, int nfaces, int size, float *out_dev,
                              void *stream);
+
+/* ---- torchvision bottleneck ResNet (csrc/resnet.hip; meerqat/image/embedding.py: resnet50 cut before avgpool + AdaptiveMaxPool2d(1), the
+ * `imagenet-RN50` column).  NHWC; activations that only feed convolutions are split pairs in PAIR LAYOUT; the BatchNorm behind each
+ * convolution is folded into W / bias by the caller.  The 3 x 3 convolutions are mq_conv3x3_pair_f32 with a zero PReLU slope (= ReLU).
+ * mq_conv1x1_pair_f32: a 1 x 1 convolution, stride 1 or 2, no padding, as an implicit GEMM on the input pair (the strided form reads
+ *   the pixels at even coordinates; nothing is copied), three bf16 MFMA products per fp32 product in the order of mq_gemm_nt_bf16x3s_f32.
+ *   Xh / Xl       input pair, PAIR LAYOUT over [B * H * W, C] (C a multiple of 32)
+ *   Wh / Wl       mq_split_bf16_tiled_f32 of W [N, C] (N a multiple of 64); bias_dev [N]
+ *   per element   v = acc + bias;  v += residual (fp32 [M, N], M = B * Ho * Wo, Ho = (H - 1) / stride + 1; may be NULL);
+ *                 v = max(v, 0) when relu != 0;  Y = v (fp32 [M, N]) and P = split(v) (PAIR LAYOUT over [M, N]): either may be NULL, not both
+ *   zeros_dev     at least 16 bytes of zeros on the device (the source of the tile rows beyond M)
+ *   tile          MQ_CONV_TILE_AUTO | _256x256 | _256x128 | _512x64 (the column count must divide N)
+ * mq_stem_conv7x7_pool_f32: the stem -- convolution 7 x 7, stride 2, padding 3, 3 -> 64 channels, + bias, ReLU, max-pool 3 x 3 stride 2
+ *   padding 1 -- in one kernel on the vector ALU; the un-pooled tensor is never stored.  x_dev fp32 NCHW [B, 3, H, W] (H a multiple of
+ *   4, W of 8: MQ_EUNSUPPORTED otherwise); wt_dev fp32 [147, 64], row (kh * 7 + kw) * 3 + c, bn1 folded in; bias_dev [64]; fp32 fused
+ *   multiply-adds in (kh, c, kw) order starting from the bias.  Ph / Pl: PAIR LAYOUT over [B * H/4 * W/4, 64].
+ * mq_pool_hw_f32: out[b, c] = max (MQ_POOL_MAX) or mean (MQ_POOL_MEAN) over p of X[b * HW + p, c], X fp32 [B * HW, C], B <= 65535.  The
+ *   mean is the fp32 sum in the order p = 0 ... HW - 1 (one rounding per pixel), divided once by HW. */
+#define MQ_POOL_MAX 0
+#define MQ_POOL_MEAN 1
+int mq_conv1x1_pair_f32(const uint16_t *Xh_dev, const uint16_t *Xl_dev, int B, int H, int W, int C, int stride,
+                        const uint16_t *Wh_dev, const uint16_t *Wl_dev, int N, const float *bias_dev, const float *residual_dev,
+                        int relu, float *Y_dev, uint16_t *Ph_dev, uint16_t *Pl_dev, const void *zeros_dev, int tile, void *stream);
+int mq_stem_conv7x7_pool_f32(const float *x_dev, int B, int H, int W, const float *wt_dev, const float *bias_dev, uint16_t *Ph_dev,
+                             uint16_t *Pl_dev, void *stream);
+int mq_pool_hw_f32(const float *X_dev, int B, int HW, int C, int mode, float *out_dev, void *stream);
 
 /* ---- reader: MultiPassageBERT answer extraction (csrc/reader.hip; the evaluation path of meerqat/train/trainee.py:742-824) ----
  * N questions, M passages each, L tokens per (question, passage) pair; every array is dense fp32 / int64, row-major.

@@ -57,6 +57,10 @@ SIGNATURES = {
     "mq_stem_conv3x3_f16": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mq_conv1x1_f16": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mq_head_prep_f16": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mq_conv1x1_pair_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
+                                    c_ptr, c_ptr, c_int, c_ptr]),
+    "mq_stem_conv7x7_pool_f32": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mq_pool_hw_f32": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "mq_gemm_nt_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "mq_split_bf16_f32": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     "mq_split_bf16_tiled_elems": (c_i64, [c_int, c_int]),

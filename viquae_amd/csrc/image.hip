@@ -292,6 +292,9 @@ int mq_image_plan(const int64_t* sizes_host, int n_images, int resize_mode, int 
                   int filter, int64_t* geom_host, int64_t* totals_host) {
     if (!sizes_host || !geom_host || !totals_host || n_images < 0 || crop_h < 1 || crop_w < 1) return MQ_EINVAL;
     if (filter != MQ_IMAGE_BICUBIC && filter != MQ_IMAGE_BILINEAR) return MQ_EUNSUPPORTED;
+    // torchvision's CenterCrop origin: int(round(d / 2.0)), Python's round-half-to-even -- one more than d / 2 when d = 3 (mod 4)
+    const bool tv_crop = (resize_mode & MQ_IMAGE_CROP_TORCHVISION) != 0;
+    resize_mode &= ~MQ_IMAGE_CROP_TORCHVISION;
     if (resize_mode != MQ_IMAGE_RESIZE_NONE && resize_mode != MQ_IMAGE_RESIZE_SHORTEST && resize_mode != MQ_IMAGE_RESIZE_EXACT)
         return MQ_EINVAL;
     if (resize_mode != MQ_IMAGE_RESIZE_NONE && (size_h < 1 || (resize_mode == MQ_IMAGE_RESIZE_EXACT && size_w < 1))) return MQ_EINVAL;
@@ -315,8 +318,8 @@ int mq_image_plan(const int64_t* sizes_host, int n_images, int resize_mode, int 
         int64_t* g = geom_host + (size_t)b * G;
         g[G_SRC] = src;
         g[G_INH] = h; g[G_INW] = w; g[G_OUTH] = oh; g[G_OUTW] = ow;
-        g[G_TOP] = (oh - crop_h) / 2;
-        g[G_LEFT] = (ow - crop_w) / 2;
+        g[G_TOP] = (oh - crop_h) / 2 + (tv_crop && ((oh - crop_h) & 3) == 3);
+        g[G_LEFT] = (ow - crop_w) / 2 + (tv_crop && ((ow - crop_w) & 3) == 3);
         g[G_KH] = resample_ksize((int)w, (int)ow, filter);
         g[G_KV] = resample_ksize((int)h, (int)oh, filter);
         g[G_COEFH] = coef; coef += (int64_t)crop_w * g[G_KH];

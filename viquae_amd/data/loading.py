@@ -25,6 +25,9 @@ DATA_ROOT_PATH = Path(os.environ.get("VIQUAE_DATA_ROOT", "data")).resolve()
 # the transform of experiments/image_embedding/clip/vit_config.json ("CLIPFeatureExtractor", gone from transformers 5;
 # "CLIPImageProcessor" is its successor) runs on the device too
 _IMAGE_PROCESSORS = ("CLIPFeatureExtractor", "CLIPImageProcessor")
+# the device-side form of the reference's torchvision transform (get_transform): built from keyword arguments alone, so
+# `pretrained_model_name_or_path: null` is its normal spelling
+_KEYWORD_TRANSFORMS = ("TorchvisionTransformHIP",)
 
 
 def get_class_from_name(class_name):
@@ -34,6 +37,9 @@ def get_class_from_name(class_name):
     if class_name in _IMAGE_PROCESSORS:
         from ..image.preprocess import CLIPImageProcessorHIP
         return CLIPImageProcessorHIP
+    if class_name in _KEYWORD_TRANSFORMS:
+        from ..image import preprocess
+        return getattr(preprocess, class_name)
     import transformers
     Class = getattr(transformers, class_name, None)
     if Class is not None:
@@ -46,6 +52,8 @@ def get_pretrained(class_name, pretrained_model_name_or_path, **kwargs):
     if pretrained_model_name_or_path is None:
         if class_name in _encoders.HIP_CLASSES:
             raise ValueError("random initialisation is a training feature: the HIP encoders load a checkpoint")
+        if class_name in _KEYWORD_TRANSFORMS:
+            return Class.from_pretrained(None, **kwargs)
         model = Class(Class.config_class(**kwargs))
         print(f"Randomly initialized model:\n{model}")
     else:

@@ -1108,6 +1108,9 @@ HIP_CLASSES = {"DPRContextEncoder": DPRContextEncoder, "DPRQuestionEncoder": DPR
                "MultiPassageBERT": MultiPassageBERT}
 
 
+from . import resnet as _resnet  # noqa: E402,F401  registers TorchvisionResNet in HIP_CLASSES (resnet.py imports this module: last)
+
+
 def __getattr__(name):
     """``viquae_amd.encoders.ArcFaceR50`` (the face encoder lives in viquae_amd/arcface.py, which imports this module)."""
     if name == "ArcFaceR50":

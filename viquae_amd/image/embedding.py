@@ -1,9 +1,17 @@
-"""Mirror of ``meerqat.image.embedding`` for the ``type: "transformers"`` branch (SURVEY.md
-section 8 a8): ``get_model_and_transform`` (:97-122), ``embed`` (:125-166), ``dataset_embed``
-(:169-183).  The model is :class:`viquae_amd.encoders.CLIPModel`; the transform is the Hugging Face
-feature extractor named in the config, which resolves to the device-side
-:class:`viquae_amd.image.preprocess.CLIPImageProcessorHIP` (Pillow-exact resize / crop / normalise on the GPU).
-torchvision / openai-clip / torchscript model types are outside this build and raise."""
+"""Mirror of ``meerqat.image.embedding``: ``get_model_and_transform`` (:97-122), ``embed`` (:125-166), ``dataset_embed``
+(:169-183).  Every model is reached through ``type: "transformers"``, as a HIP class named in the config:
+
+* ``class_name: "CLIPModel"`` (experiments/image_embedding/clip/vit_config.json) -> :class:`viquae_amd.encoders.CLIPModel`, with
+  the Hugging Face feature extractor named in the config as its transform, which resolves to the device-side
+  :class:`viquae_amd.image.preprocess.CLIPImageProcessorHIP` (Pillow-exact resize / crop / normalise on the GPU);
+* ``class_name: "TorchvisionResNet"`` (the shipped experiments/image_embedding/imagenet/config.json with ``type`` and
+  ``class_name`` added to its ``model_kwargs``: the ``imagenet-RN50`` column) -> :class:`viquae_amd.resnet.TorchvisionResNet`,
+  torchvision's bottleneck ResNet from a local state-dict file, with ``transform_kwargs: {"class_name":
+  "TorchvisionTransformHIP", "pretrained_model_name_or_path": null}`` -> the device-side form of the reference's torchvision
+  transform, :class:`viquae_amd.image.preprocess.TorchvisionTransformHIP`.
+
+``type: "torchvision"`` (the reference builds the model with torchvision and may download its weights), ``"clip"`` (openai-clip)
+and ``"torchscript"`` are outside this build and raise."""
 import numpy as np
 import torch
 

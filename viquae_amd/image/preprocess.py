@@ -38,6 +38,7 @@ class CLIPImageProcessorHIP:
     do_normalize, image_mean, image_std, do_convert_rgb."""
     on_device = True  # embed() must not ship this transform to a multiprocessing pool
     model_input_names = ["pixel_values"]
+    crop_rule = 0     # OR-ed into mq_image_plan's resize mode: 0 = transformers' centre crop, (size - crop) // 2
 
     def __init__(self, do_resize=True, size=224, resample=3, do_center_crop=True, crop_size=224, do_rescale=True,
                  rescale_factor=1 / 255, do_normalize=True, image_mean=(0.48145466, 0.4578275, 0.40821073),
@@ -100,7 +101,7 @@ class CLIPImageProcessorHIP:
         B = sizes.shape[0]
         geom = np.zeros((B, 12), dtype=np.int64)
         totals = np.zeros(5, dtype=np.int64)
-        mode = 0 if not self.do_resize else (1 if self.size_mode == "shortest" else 2)
+        mode = (0 if not self.do_resize else (1 if self.size_mode == "shortest" else 2)) | self.crop_rule
         _lib.check(lib.mq_image_plan(sizes.ctypes.data, B, mode, self.size_h, self.size_w, self.crop_h, self.crop_w,
                                      self.resample, geom.ctypes.data, totals.ctypes.data), "mq_image_plan")
         return geom, totals
@@ -185,3 +186,60 @@ class CLIPImageProcessorHIP:
             from concurrent.futures import ThreadPoolExecutor
             pool = self._threads = ThreadPoolExecutor(self._PACK_THREADS)
         return pool
+
+
+class TorchvisionTransformHIP(CLIPImageProcessorHIP):
+    """Device-side form of the reference's torchvision transform (meerqat/image/embedding.py:86-94, ``get_transform``):
+    ``Resize(**resize_kwargs)`` -> ``CenterCrop(crop_size)`` -> ``ToTensor()`` -> ``Normalize(mean, std)`` on PIL images, same
+    keyword arguments and defaults.  The resize, the packing and the kernels are :class:`CLIPImageProcessorHIP`'s; two rules are
+    torchvision's own:
+
+    * the crop origin is ``int(round((size - crop) / 2.0))`` with Python's round-half-to-even (``MQ_IMAGE_CROP_TORCHVISION``), one
+      more than transformers' ``(size - crop) // 2`` when ``size - crop`` is 3 modulo 4 (a 224 x 231 image: left = 4, not 3);
+    * ``ToTensor`` is ``float32(u8) / 255`` in fp32 and ``Normalize`` ``(x - mean) / std`` in fp32.  The kernel's table holds
+      ``(float32(float64(u8) * (1 / 255)) - mean) / std``: for all 256 bytes the two first factors are the same float32 (the
+      double product is within 2^-53 relative of u8 / 255, far from any float32 rounding boundary of these 256 quotients;
+      tests/test_resnet_cpu.py checks all of them), so the table implements torchvision's rule exactly.
+
+    ``resize_kwargs``: ``size`` (an int = shortest edge, the long edge ``int(size * long / short)``; a pair (h, w) = exact) and
+    ``interpolation`` (bilinear, the default, or bicubic; 2 / 3 or the name); ``max_size``, and images smaller than the crop window
+    (torchvision pads them), raise NotImplementedError."""
+    crop_rule = 0x100  # MQ_IMAGE_CROP_TORCHVISION
+
+    def __init__(self, resize_kwargs=None, crop_size=224, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device=None):
+        kw = dict(size=224) if resize_kwargs is None else dict(resize_kwargs)
+        size, interpolation = kw.pop("size"), kw.pop("interpolation", "bilinear")
+        if kw.pop("max_size", None) is not None:
+            raise NotImplementedError("Resize(max_size=...) is not provided")
+        kw.pop("antialias", None)  # PIL images are always resampled with Pillow's (antialiasing) filters
+        if kw:
+            raise TypeError(f"unexpected resize_kwargs: {sorted(kw)}")
+        if isinstance(size, (list, tuple)) and len(size) == 1:
+            size = size[0]
+        interpolation = getattr(interpolation, "value", interpolation)  # an InterpolationMode: its name
+        if isinstance(interpolation, str) and interpolation.lower() not in _RESAMPLE_NAMES:
+            raise NotImplementedError(f"interpolation={interpolation!r}: bilinear and bicubic are provided")
+        super().__init__(size=size, resample=interpolation, crop_size=crop_size, image_mean=mean, image_std=std, device=device)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path=None, **kwargs):
+        """``None``: the keyword arguments alone (the reference's defaults otherwise); a path: a JSON file (or a directory holding
+        ``preprocessor_config.json``) of those keyword arguments, updated by ``kwargs``."""
+        cfg = {}
+        if pretrained_model_name_or_path is not None:
+            path = str(pretrained_model_name_or_path)
+            if os.path.isdir(path):
+                path = os.path.join(path, "preprocessor_config.json")
+            with open(path) as f:
+                cfg = json.load(f)
+        cfg.update(kwargs)
+        return cls(**cfg)
+
+    def plan(self, sizes):
+        try:
+            return super().plan(sizes)
+        except _lib.MeerqatHipError as e:
+            if "unsupported" in str(e).lower():
+                raise NotImplementedError("an image is smaller than the crop window after Resize: torchvision pads it, which is "
+                                          "not provided") from e
+            raise
