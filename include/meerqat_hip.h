@@ -703,6 +703,34 @@ int mq_stem_conv7x7_pool_f32(const float *x_dev, int B, int H, int W, const floa
                              uint16_t *Pl_dev, void *stream);
 int mq_pool_hw_f32(const float *X_dev, int B, int HW, int C, int mode, float *out_dev, void *stream);
 
+/* ---- openai-clip's ModifiedResNet (csrc/clip_resnet.hip; `clip.load("RN50")`'s visual tower, the `clip-RN50` column).  The bottlenecks
+ * are mq_conv1x1_pair_f32 / mq_conv3x3_pair_f32 at stride 1 with these around them; all four run on the vector ALU.
+ * mq_clip_stem_conv3x3s2_f32: the stem's first convolution -- 3 x 3, stride 2, padding 1, 3 -> N channels (N = 32: MQ_EUNSUPPORTED
+ *   otherwise), + bias, ReLU.  x_dev fp32 NCHW [B, 3, H, W] (H, W even: MQ_EUNSUPPORTED otherwise); wt_dev fp32 [27, N], row
+ *   (kh * 3 + kw) * 3 + c, bn1 folded in; bias_dev [N]; fp32 fused multiply-adds in (kh, c, kw) order starting from the bias.
+ *   Ph / Pl: PAIR LAYOUT over [B * H/2 * W/2, N].
+ * mq_avgpool2x2_pair_f32: nn.AvgPool2d(2) on a pair.  Xh / Xl: PAIR LAYOUT over [B * H * W, C] (NHWC; H, W even, C a multiple of 32:
+ *   MQ_EINVAL otherwise); Ph / Pl: PAIR LAYOUT over [B * H/2 * W/2, C].  With x_ij = hi + lo (exact in fp32) of input pixel
+ *   (2 ho + i, 2 wo + j): out = split((((x00 + x01) + x10) + x11) * 0.25f), every operation one fp32 rounding.
+ * mq_attnpool_tokens_f32: AttentionPool2d's token matrix from the last block's fp32 output Y [B * HW, C] and the positional embedding
+ *   pos_dev fp32 [HW + 1, C] (C a multiple of 32; Y and pos 16-byte aligned).  T / Th, Tl: PAIR LAYOUT over [B * (HW + 1), C];
+ *   row b * (HW + 1) = mean_b + pos[0] with mean_b mq_pool_hw_f32's MQ_POOL_MEAN (the fp32 sum in the order p = 0 ... HW - 1, divided
+ *   once by HW), rows b * (HW + 1) + 1 + p = Y[b * HW + p] + pos[1 + p].  Qh / Ql: PAIR LAYOUT over [B, C], row b = the mean token of
+ *   image b once more (the operand of q_proj).
+ * mq_attention_single_query_f32: multi-head attention with ONE query per image: q_dev fp32 [B, heads * 64], kv_dev fp32
+ *   [B * T, 2 * heads * 64] = [k | v] projections of the T tokens of every image.  Per (image, head), in fp32:
+ *   s_t = (q . k_t) * scale, the 64 products summed by a butterfly over the lanes (xor 32, 16, ..., 1);  p_t = expf(s_t - max s);
+ *   o = (sum over t = 0 ... T - 1 in that order of p_t v_t) / (sum of p_t).  Oh / Ol: PAIR LAYOUT over [B, heads * 64].
+ *   head_dim must be 64 and T <= 8192 (MQ_EUNSUPPORTED otherwise); T is a runtime value. */
+int mq_clip_stem_conv3x3s2_f32(const float *x_dev, int B, int H, int W, const float *wt_dev, const float *bias_dev, int N,
+                               uint16_t *Ph_dev, uint16_t *Pl_dev, void *stream);
+int mq_avgpool2x2_pair_f32(const uint16_t *Xh_dev, const uint16_t *Xl_dev, int B, int H, int W, int C, uint16_t *Ph_dev,
+                           uint16_t *Pl_dev, void *stream);
+int mq_attnpool_tokens_f32(const float *Y_dev, int B, int HW, int C, const float *pos_dev, uint16_t *Th_dev, uint16_t *Tl_dev,
+                           uint16_t *Qh_dev, uint16_t *Ql_dev, void *stream);
+int mq_attention_single_query_f32(const float *q_dev, const float *kv_dev, int B, int T, int heads, int head_dim, float scale,
+                                  uint16_t *Oh_dev, uint16_t *Ol_dev, void *stream);
+
 /* ---- reader: MultiPassageBERT answer extraction (csrc/reader.hip; the evaluation path of meerqat/train/trainee.py:742-824) ----
  * N questions, M passages each, L tokens per (question, passage) pair; every array is dense fp32 / int64, row-major.
  * mq_reader_qa_head_f32: BertForQuestionAnswering.qa_outputs on the last hidden states h [rows, H] (H a multiple of 4; h and w

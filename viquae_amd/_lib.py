@@ -61,6 +61,10 @@ SIGNATURES = {
                                     c_ptr, c_ptr, c_int, c_ptr]),
     "mq_stem_conv7x7_pool_f32": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mq_pool_hw_f32": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "mq_clip_stem_conv3x3s2_f32": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
+    "mq_avgpool2x2_pair_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "mq_attnpool_tokens_f32": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mq_attention_single_query_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, ctypes.c_float, c_ptr, c_ptr, c_ptr]),
     "mq_gemm_nt_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "mq_split_bf16_f32": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     "mq_split_bf16_tiled_elems": (c_i64, [c_int, c_int]),

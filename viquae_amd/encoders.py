@@ -1109,6 +1109,7 @@ HIP_CLASSES = {"DPRContextEncoder": DPRContextEncoder, "DPRQuestionEncoder": DPR
 
 
 from . import resnet as _resnet  # noqa: E402,F401  registers TorchvisionResNet in HIP_CLASSES (resnet.py imports this module: last)
+from . import clip_resnet as _clip_resnet  # noqa: E402,F401  registers CLIPModifiedResNet (it builds on resnet.py)
 
 
 def __getattr__(name):

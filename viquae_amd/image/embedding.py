@@ -10,8 +10,12 @@
   "TorchvisionTransformHIP", "pretrained_model_name_or_path": null}`` -> the device-side form of the reference's torchvision
   transform, :class:`viquae_amd.image.preprocess.TorchvisionTransformHIP` (INTEGRATION.md).
 
-``type: "torchvision"`` (the reference builds the model with torchvision and may download its weights), ``"clip"`` (openai-clip)
-and ``"torchscript"`` are outside this build and raise."""
+* ``class_name: "CLIPModifiedResNet"`` (the ``clip-RN50`` column; INTEGRATION.md gives the config that stands in for
+  experiments/image_embedding/clip/config.json) -> :class:`viquae_amd.clip_resnet.CLIPModifiedResNet`, openai-clip's ResNet tower
+  from a local weight file, with ``TorchvisionTransformHIP`` at bicubic 224 and CLIP's mean / std as its transform.
+
+``type: "torchvision"`` (the reference builds the model with torchvision and may download its weights), ``"clip"`` (the openai-clip
+package, which may download too) and ``"torchscript"`` are outside this build and raise."""
 import numpy as np
 import torch
 
@@ -24,8 +28,9 @@ def get_model_and_transform(model_kwargs={}, transform_kwargs={}):
     training = model_kwargs.pop("training", False)
     model_type = model_kwargs.pop("type", "torchvision")
     if model_type != "transformers":
-        raise NotImplementedError(f"model type '{model_type}' is outside the MI355X build: use type 'transformers' "
-                                  "(experiments/image_embedding/clip/vit_config.json)")
+        hint = ("experiments/image_embedding/clip/vit_config.json" if model_type != "clip" else
+                "for clip's RN50 / RN101: class_name 'CLIPModifiedResNet' with a local weight file, INTEGRATION.md, the clip-RN50 config")
+        raise NotImplementedError(f"model type '{model_type}' is outside the MI355X build: use type 'transformers' ({hint})")
     model = get_pretrained(**model_kwargs)
     transform = get_pretrained(**transform_kwargs)
     model = model.to(device).train(training)

@@ -88,16 +88,7 @@ class TorchvisionResNet(_HipEncoder):
             if f"layer{s}.{n - 1}.conv1.weight" not in state or f"layer{s}.{n}.conv1.weight" in state:
                 raise ValueError(f"the state dict does not have layers={self.layers} blocks (stage {s})")
         self._geom = {}
-
-        def conv(name, bn, k, stride):
-            w = state[name + ".weight"]
-            if w.ndim != 4 or w.shape[2] != k or w.shape[3] != k:
-                raise ValueError(f"{name}.weight: expected a {k} x {k} kernel, got {w.shape}")
-            w64, b64 = fold_conv_bn(w, _arcface._affine(state, bn))
-            cout, cin = w.shape[:2]
-            self._geom[name] = (cout, cin, k, stride)
-            self._reg(name + ".w2", torch.from_numpy(w64.transpose(0, 2, 3, 1).reshape(cout, -1).astype(np.float32)))   # (kh, kw, c)
-            self._reg(name + ".b", torch.from_numpy(b64.astype(np.float32)))
+        conv = lambda name, bn, k, stride: self._fold(state, name, bn, k, stride)  # noqa: E731
 
         if state["conv1.weight"].shape != (64, 3, 7, 7):
             raise ValueError(f"conv1.weight: expected [64, 3, 7, 7], got {state['conv1.weight'].shape}")
@@ -144,8 +135,22 @@ class TorchvisionResNet(_HipEncoder):
 
     def train(self, mode=True):
         if mode:
-            raise NotImplementedError("TorchvisionResNet is an inference encoder: BatchNorms are folded, eval mode only")
+            raise NotImplementedError(f"{type(self).__name__} is an inference encoder: BatchNorms are folded, eval mode only")
         return super().train(False)
+
+    def _fold(self, state, name, bn, k, stride, pad_out=0, pad_in=0):
+        """Registers convolution ``name`` with the BatchNorm ``bn`` behind it folded in (float64): ``.w2`` fp32 [Cout, k k Cin] with
+        (kh, kw, c) columns, ``.b`` fp32 [Cout], and its geometry.  ``pad_out`` / ``pad_in``: output / input channels of zeros added
+        (a padded output channel is relu(0) = 0, a padded input channel multiplies it by 0)."""
+        w = state[name + ".weight"]
+        if w.ndim != 4 or w.shape[2] != k or w.shape[3] != k:
+            raise ValueError(f"{name}.weight: expected a {k} x {k} kernel, got {w.shape}")
+        w64, b64 = fold_conv_bn(w, _arcface._affine(state, bn))
+        w64, b64 = np.pad(w64, ((0, pad_out), (0, pad_in), (0, 0), (0, 0))), np.pad(b64, (0, pad_out))
+        cout, cin = w64.shape[:2]
+        self._geom[name] = (cout, cin, k, stride)
+        self._reg(name + ".w2", torch.from_numpy(w64.transpose(0, 2, 3, 1).reshape(cout, -1).astype(np.float32)))   # (kh, kw, c)
+        self._reg(name + ".b", torch.from_numpy(b64.astype(np.float32)))
 
     # ------------------------------------------------------------------ kernels
     def _b(self, name):
@@ -226,25 +231,39 @@ class TorchvisionResNet(_HipEncoder):
             out = self._forward(x)
         return out.view(x.shape[0], self.num_features, 1, 1)
 
+    _avgpooled = frozenset()   # blocks whose stride is an AvgPool2d(2) (openai-clip's ModifiedResNet, clip_resnet.py); none here
+
+    def _avgpool(self, xin, B, H, W):
+        raise NotImplementedError
+
     def bottleneck(self, p, xin, y, B, H, W, want_y=True, want_pair=True):
         """One block ``p`` on its input pair ``xin`` (and fp32 shortcut ``y``, unused when the block has a downsample) -> (y', pair',
-        Ho, Wo).  (The walk a ModifiedResNet of openai-clip would share: its blocks are these with an average pool in front of conv3.)"""
+        Ho, Wo).  openai-clip's ModifiedResNet walks the same block: its strided blocks (``_avgpooled``) keep every convolution at
+        stride 1 and average-pool 2 x 2 in front of conv3 and of the shortcut's 1 x 1."""
         (_, o1), _, _ = self._conv1x1(p + ".conv1", xin, B, H, W)
         o2, Ho, Wo = self._conv3x3(p + ".conv2", o1, B, H, W)
+        if p in self._avgpooled:
+            o2, xin = self._avgpool(o2, B, Ho, Wo), self._avgpool(xin, B, H, W)
+            H, W, Ho, Wo = H // 2, W // 2, Ho // 2, Wo // 2
         if (p + ".downsample.0") in self._geom:
             (y, _), _, _ = self._conv1x1(p + ".downsample.0", xin, B, H, W, relu=False, want_y=True, want_pair=False)
         (y, xin), _, _ = self._conv1x1(p + ".conv3", o2, B, Ho, Wo, residual=y, want_y=want_y, want_pair=want_pair)
         return y, xin, Ho, Wo
 
-    def _forward(self, x):
-        B, H, W = x.shape[0], x.shape[2] // 4, x.shape[3] // 4
+    def _stages(self, xin, B, H, W):
+        """the four stages on the stem's output pair ``xin`` [B * H * W, C] -> (the last block's fp32 output, H', W')"""
         blocks = [f"layer{s}.{i}" for s, n in enumerate(self.layers, start=1) for i in range(n)]
-        xin, y = self._stem(x), None
+        y = None
         for bi, p in enumerate(blocks):
             last = bi + 1 == len(blocks)
             # the fp32 output is the NEXT block's shortcut (not read when that block has a downsample) or the pooled head's input
             reads_y = last or (blocks[bi + 1] + ".downsample.0") not in self._geom
             y, xin, H, W = self.bottleneck(p, xin, y, B, H, W, want_y=reads_y, want_pair=not last)
+        return y, H, W
+
+    def _forward(self, x):
+        B, H, W = x.shape[0], x.shape[2] // 4, x.shape[3] // 4
+        y, H, W = self._stages(self._stem(x), B, H, W)
         return self._pool(y, B, H * W)
 
 
