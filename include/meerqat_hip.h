@@ -353,6 +353,10 @@ int mq_clip_text_embed_packed_f32(const int64_t *input_ids_dev, const int32_t *p
  *   mq_bert_embed_ln_split_f32 mq_bert_embed_ln_f32 writing fp32 and, optionally, the pair
  *   mq_attention_split_f32     mq_attention_causal_f32 writing fp32 (may be NULL) and/or the pair; bf16x3 != 0 computes
  *                              q.k and p.v as three-term split-bf16 products on the bf16 matrix pipe (fp32-class accuracy)
+ *                              A sequence whose attention_mask row has no live key (all zeros) attends UNIFORMLY to all its
+ *                              L keys -- every context row is the mean of its L value rows -- as Hugging Face BERT does by
+ *                              adding finfo.min to the logits; every other sequence keeps its bits.  causal != 0 together with
+ *                              such a row is undefined.  (The same holds for mq_attention_f32 / mq_attention_causal_f32.)
  * PAIR LAYOUT: the two arrays of a pair [M, K] are stored tile by tile -- element (row, col) at
  * [row / 256][col / 32][row % 256][col % 32] -- so that the operand of one K step of a GEMM tile is one contiguous 16-KiB
  * block (the layout of mq_split_bf16_tiled_f32, which can mint such a pair from an fp32 matrix).  Each array holds

@@ -887,6 +887,17 @@ __global__ void clip_patchify_kernel(const float* __restrict__ px, float* __rest
 
 constexpr int DH = 64;  // attention head size
 
+// A sequence whose padding mask has NO live key attends uniformly to all its L keys, as Hugging Face BERT does: it adds
+// finfo.min to every masked logit, which absorbs the logit, and the softmax of L equal values is 1 / L (oracle/encoders.py
+// bert_forward).  Both attention kernels take that case as "scale 0, every key live".  Block-uniform (every thread of the
+// workgroup calls it); only launches with a mask pay for the scan, and a sequence with a live key keeps every bit.  Causal
+// attention over such a sequence is undefined (the CLIP oracle yields NaN there).
+__device__ __forceinline__ bool attention_no_live_key(const long long* __restrict__ mask_row, int L, int tid, int nthr) {
+    int live = 0;
+    for (int j = tid; j < L; j += nthr) live |= (mask_row[j] != 0);
+    return !__syncthreads_or(live);
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // MFMA attention (fp32): one workgroup (4 waves) per (sequence, head, block of 128 queries).
@@ -921,6 +932,8 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int nthr = blockDim.x;  // 64 * min(4, ceil(queries of this block / 32)) threads: no wave without queries
     const int i = lane & 31, kh = lane >> 5;
+    const bool uniform = mask && attention_no_live_key(mask + row0, L, tid, nthr);
+    if (uniform) scale = 0.f;  // every logit 0 and (below) every key of the sequence live
     const int qrow = blockIdx.y * 128 + 32 * w + i;   // this lane's query
     float qreg[32];
 #pragma unroll
@@ -945,7 +958,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(const float* __rest
         *reinterpret_cast<float4*>(Vs + j * 64 + c4) = vf;
     }
     for (int j = tid; j < NK; j += nthr)
-        addm[j] = (kb0 + j < L && (!mask || mask[row0 + kb0 + j] != 0)) ? 0.f : -INFINITY;
+        addm[j] = (kb0 + j < L && (!mask || uniform || mask[row0 + kb0 + j] != 0)) ? 0.f : -INFINITY;
     __syncthreads();
 
     f32x16 sacc[NKT];
@@ -1068,6 +1081,8 @@ __global__ __launch_bounds__(WIDE ? 512 : 256) void attention_x3_kernel(const fl
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int nthr = blockDim.x;
     const int i = lane & 31, kg = lane >> 5;
+    const bool uniform = mask && attention_no_live_key(mask + row0, L, tid, nthr);
+    if (uniform) scale = 0.f;  // every logit 0 and (below) every key of the sequence live
     const int qpb = nthr >> 1;                         // queries per workgroup: 32 per wave
     const bool wave_active = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * qpb + 32 * w)) < L;
     // key tiles that hold at least one key of this sequence (block-uniform).  A packed sequence of 150 tokens in the
@@ -1145,7 +1160,7 @@ __global__ __launch_bounds__(WIDE ? 512 : 256) void attention_x3_kernel(const fl
         }
     }
     for (int j = tid; j < NK; j += nthr)
-        addm[j] = (kb0 + j < L && (!mask || mask[row0 + kb0 + j] != 0)) ? 0.f : -INFINITY;
+        addm[j] = (kb0 + j < L && (!mask || uniform || mask[row0 + kb0 + j] != 0)) ? 0.f : -INFINITY;
     __syncthreads();
 
     if (wave_active) {  // wave-uniform: a wave without queries (short sequence in a wide workgroup) only helps staging
