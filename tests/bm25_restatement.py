@@ -1,0 +1,248 @@
+"""CPU restatement of the BM25 search (viquae_amd/ir/bm25.py, csrc/bm25.hip) in numpy, written independently of the product: a
+character-by-character ``standard`` tokeniser, Lucene's one-byte length code, the BM25Similarity statistics, a dense fp32
+accumulator filled clause by clause (multiply, then add: two roundings), and the top-k as a sort of the 64-bit keys
+(score bits << 32) | (id_asc ? ~id : id).  The GPU tests compare with it bit for bit; tests/test_bm25_cpu.py checks it against a
+worked example.  Also here: the synthetic corpora and query sets the two test modules share."""
+import functools
+import math
+import unicodedata
+
+import numpy as np
+
+K_VALUES = (1, 100, 2048)
+ZIPF_TERMS = 500
+# term ids behind the Zipfian vocabulary, placed by hand (see corpus())
+T_EVERY, T_LAST, T_BLOCK_END, T_BLOCK_START, T_UNUSED = 500, 501, 502, 503, 504
+VOCABULARY_SIZE = 505
+
+
+# ---------------------------------------------------------------------------------------------------------------- analysis
+def _kind(ch):
+    cp = ord(ch)
+    cat = unicodedata.category(ch)
+    cjk = (0x3040 <= cp <= 0x30FF or 0x31F0 <= cp <= 0x31FF or 0xFF66 <= cp <= 0xFF9F or 0x4E00 <= cp <= 0x9FFF
+           or 0x3400 <= cp <= 0x4DBF or 0xF900 <= cp <= 0xFAFF or 0x20000 <= cp <= 0x2FA1F or cp in (0x3005, 0x3007))
+    if ch == "_":
+        return "underscore"
+    if cjk and (cat.startswith("L") or cat == "Nl"):
+        return "cjk"
+    if cat.startswith("L"):
+        return "letter"
+    if cat == "Nd":
+        return "digit"
+    if cat.startswith("M") or cat == "Cf":
+        return "extend"
+    return "other"
+
+
+def tokenize(text):
+    """The ``standard`` analyzer's rules as the issue states them, as an explicit scan."""
+    chars = list(text)
+    kinds, prev = [], "other"
+    for ch in chars:
+        k = _kind(ch)
+        if k == "extend":  # stays with what it follows
+            k = prev if prev in ("letter", "digit", "underscore", "cjk+") else ("cjk+" if prev == "cjk" else "other")
+        kinds.append(k)
+        prev = k
+    n, i, runs = len(chars), 0, []
+    while i < n:
+        if kinds[i] == "cjk":
+            j = i + 1
+            while j < n and kinds[j] == "cjk+":
+                j += 1
+            runs.append((i, j))
+            i = j
+            continue
+        if kinds[i] not in ("letter", "digit", "underscore"):
+            i += 1
+            continue
+        j, has_alnum = i, False
+        while j < n:
+            if kinds[j] in ("letter", "digit", "underscore"):
+                has_alnum = has_alnum or kinds[j] != "underscore"
+                j += 1
+                continue
+            joins = False
+            if 0 < j < n - 1 and j > i:
+                before, after = kinds[j - 1], kinds[j + 1]
+                if chars[j] in "'.:" and before == "letter" and after == "letter":
+                    joins = True
+                if chars[j] in ".,;" and before == "digit" and after == "digit":
+                    joins = True
+            if not joins:
+                break
+            j += 1
+        if has_alnum:
+            runs.append((i, j))
+        i = j
+    out = []
+    for s, e in runs:
+        for c in range(s, e, 255):
+            out.append("".join(chars[c:min(c + 255, e)]).lower())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- length code
+def encode_length(n):
+    """SmallFloat.intToByte4."""
+    if n < 24:
+        return n
+    m = n - 24
+    bits = m.bit_length()
+    if bits < 4:
+        return 24 + m
+    shift = bits - 4
+    return 24 + (((m >> shift) & 7) | ((shift + 1) << 3))
+
+
+def decode_length(c):
+    """SmallFloat.byte4ToInt."""
+    if c < 24:
+        return c
+    e = c - 24
+    low, shift = e & 7, (e >> 3) - 1
+    return 24 + (low if shift < 0 else (low | 8) << shift)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the index
+class Restatement:
+    """BM25 over documents given as integer term-id sequences."""
+
+    def __init__(self, docs, vocabulary_size, k1=1.2, b=0.75):
+        self.N, self.V = len(docs), int(vocabulary_size)
+        self.lengths = np.array([len(d) for d in docs], dtype=np.int64)
+        per_doc = [np.unique(np.asarray(d, dtype=np.int64), return_counts=True) for d in docs]
+        terms = np.concatenate([t for t, _ in per_doc]) if docs else np.zeros(0, np.int64)
+        counts = np.concatenate([c for _, c in per_doc]) if docs else np.zeros(0, np.int64)
+        owner = np.repeat(np.arange(self.N), [len(t) for t, _ in per_doc])
+        order = np.argsort(terms, kind="stable")          # by term; documents stay ascending inside a term
+        self.doc_freq = np.bincount(terms, minlength=self.V).astype(np.int64)
+        cuts = np.cumsum(self.doc_freq)[:-1]
+        self.post_docs = np.split(owner[order], cuts)     # term -> documents, ascending
+        self.post_tf = np.split(counts[order], cuts)      # term -> term frequencies
+        self.doc_count = int((self.lengths > 0).sum())
+        self.sum_total_term_freq = int(self.lengths.sum())
+        self.avgdl = np.float32(self.sum_total_term_freq / self.doc_count) if self.doc_count else np.float32(1)
+        self.codes = np.array([encode_length(int(n)) for n in self.lengths], dtype=np.uint8)
+        self.idf = np.array([math.log(1 + (self.doc_count - df + 0.5) / (df + 0.5)) for df in self.doc_freq.tolist()]).astype(np.float32)
+        self.set_bm25(k1, b)
+
+    def set_bm25(self, k1, b):
+        k1, b = np.float32(k1), np.float32(b)
+        decoded = np.array([decode_length(c) for c in range(256)], dtype=np.float32)
+        self.cache = k1 * ((np.float32(1) - b) + b * decoded / self.avgdl)
+        assert self.cache.dtype == np.float32
+        self.impacts = []
+        for docs, tf in zip(self.post_docs, self.post_tf):
+            tf = tf.astype(np.float64)
+            norm = self.cache[self.codes[docs]].astype(np.float64)
+            self.impacts.append((docs, (tf / (tf + norm)).astype(np.float32)))
+
+    def csr(self):
+        """(ptr, doc, tf, impact) in the product's layout."""
+        ptr = np.concatenate([[0], np.cumsum(self.doc_freq)]).astype(np.int64)
+        return (ptr, np.concatenate(self.post_docs).astype(np.int32), np.concatenate(self.post_tf).astype(np.int32),
+                np.concatenate([i for _, i in self.impacts]).astype(np.float32))
+
+    def clauses(self, query):
+        """[(term, weight fp32)]: distinct in-vocabulary terms that some document holds, in order of first occurrence."""
+        seen = {}
+        for t in query:
+            t = int(t)
+            if 0 <= t < self.V and self.doc_freq[t] > 0:
+                seen[t] = seen.get(t, 0) + 1
+        return [(t, np.float32(m) * self.idf[t]) for t, m in seen.items()]
+
+    def scores(self, query):
+        acc = np.zeros(self.N, dtype=np.float32)
+        for t, w in self.clauses(query):
+            docs, impact = self.impacts[t]
+            contribution = np.float32(w) * impact          # one rounding
+            acc[docs] = acc[docs] + contribution           # another
+        return acc
+
+    def hits(self, query):
+        return int(np.count_nonzero(self.scores(query)))
+
+    def search(self, queries, k, tie_order="id_asc"):
+        D = np.full((len(queries), k), -np.inf, dtype=np.float32)
+        I = np.full((len(queries), k), -1, dtype=np.int64)
+        for row, q in enumerate(queries):
+            d, i = topk(self.scores(q), k, tie_order)
+            D[row, :len(d)], I[row, :len(i)] = d, i
+        return D, I
+
+
+def topk(scores, k, tie_order="id_asc"):
+    """The best k hits (score > 0) by the 64-bit key, best first -> (scores fp32, ids int64)."""
+    ids = np.flatnonzero(scores.view(np.uint32)).astype(np.uint64)
+    low = (~ids & np.uint64(0xFFFFFFFF)) if tie_order == "id_asc" else ids
+    keys = (scores.view(np.uint32)[ids.astype(np.int64)].astype(np.uint64) << np.uint64(32)) | low
+    keys = np.sort(keys)[::-1][:k]
+    low = (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    out_ids = (~low if tie_order == "id_asc" else low).astype(np.int64)
+    return (keys >> np.uint64(32)).astype(np.uint32).view(np.float32), out_ids
+
+
+# ---------------------------------------------------------------------------------------------------------------- shared cases
+def corpus_sizes(R):
+    return (1, R - 1, R + 37, 3 * R + 1)
+
+
+def corpus(N, R, seed=0):
+    """N documents of 1 ... 300 Zipfian term ids (500 terms), seeded, plus the hand-placed terms: T_EVERY in every document, T_LAST
+    only in the last one, T_BLOCK_END in the three documents that end block 0 (when the corpus reaches them), T_BLOCK_START in the
+    three that start block 1; T_UNUSED in none (an in-range id that is out of vocabulary all the same)."""
+    rng = np.random.default_rng(seed + N)
+    lengths = rng.integers(1, 301, size=N)
+    p = 1.0 / np.arange(1, ZIPF_TERMS + 1)
+    flat = rng.choice(ZIPF_TERMS, size=int(lengths.sum()), p=p / p.sum())
+    docs = [d.tolist() for d in np.split(flat, np.cumsum(lengths)[:-1])]
+    for i, d in enumerate(docs):
+        d.append(T_EVERY)
+        if i == N - 1:
+            d.append(T_LAST)
+        if R - 3 <= i <= R - 1:
+            d.extend([T_BLOCK_END] * (1 + i % 2))
+        if R <= i <= R + 2:
+            d.append(T_BLOCK_START)
+    return [np.array(d, dtype=np.int64) for d in docs]
+
+
+def queries(nq=37, seed=1):
+    """37 queries: the special cases first, Zipfian ones of 1 ... 12 terms behind them."""
+    rng = np.random.default_rng(seed)
+    p = 1.0 / np.arange(1, ZIPF_TERMS + 1)
+    out = [
+        [0, 1, 2],                                   # the commonest terms: nearly every document
+        [T_LAST],                                    # one hit
+        [],                                          # empty
+        [T_UNUSED, VOCABULARY_SIZE + 7, -3],         # out of vocabulary three ways
+        list(range(100, 140)),                       # 40 distinct terms
+        [5, T_UNUSED, 5, 499, 5],                    # a repeated term and an unknown one
+        [T_EVERY],                                   # ties everywhere the lengths agree
+        [T_BLOCK_END], [T_BLOCK_START], [T_BLOCK_END, T_BLOCK_START, T_LAST],
+        [ZIPF_TERMS - 1],                            # the rarest Zipfian term
+    ]
+    while len(out) < nq:
+        out.append(rng.choice(ZIPF_TERMS, size=int(rng.integers(1, 13)), p=p / p.sum()).tolist())
+    return out[:nq]
+
+
+def tie_corpus(R):
+    """2R identical documents: every score ties, the order is the tie order alone and the k-th place lies inside a tied run that
+    spans the block boundary."""
+    return [np.array([3, 4, 4, 9], dtype=np.int64)] * (2 * R)
+
+
+@functools.lru_cache(maxsize=None)
+def restated(N, R, k1=1.2, b=0.75):
+    return Restatement(corpus(N, R), VOCABULARY_SIZE, k1, b)
+
+
+TEXTS = ["The quick brown fox, born in 1,000 B.C., met O'Neil at 3.14 p.m.",
+         "foo_bar is a well-known identifier; the fox was not amused.",
+         "", "Café München serves the fox: 日本語の menu!",
+         "the the the fox", "?!"]
+TEXT_QUERIES = ["the fox", "who is O'Neil?", "", "zzz qqq", "café 本 3.14 the"]

@@ -14,7 +14,8 @@ Same names, arguments and error behaviour as the reference for the hot-path surf
 What differs underneath: ``add_or_load_faiss_index`` builds a :class:`viquae_amd.index.MI355XFlatIndex`
 (HBM-resident, hand-written HIP scan) instead of a FAISS index and registers it in
 ``dataset._indexes`` so that ``Dataset.search_batch`` / ``get_nearest_examples_batch`` keep working.
-Sparse kinds (ES / PYSERINI) are outside this build's scope and raise.
+Sparse kinds served by a server (ES / PYSERINI) are outside this build's scope and raise; the text column is
+served by this build's own kind instead, ``kind: "BM25"`` -> ``add_or_load_bm25_index`` -> :class:`viquae_amd.ir.bm25.MI355XBM25Index`.
 """
 import enum
 import json
@@ -40,6 +41,7 @@ class IndexKind(enum.Enum):
     FAISS = 0
     ES = 1
     PYSERINI = 2
+    BM25 = 3  # this build's own sparse kind: exhaustive BM25 on the device (viquae_amd/ir/bm25.py); ES / PYSERINI stay out of scope
 
 
 class Index:
@@ -95,6 +97,9 @@ class KnowledgeBase:
         """Pre-process the queries as the index requires, then ``self.dataset.search_batch``.
         Returns (scores [nq,k] float32, indices [nq,k] int), rows best-first."""
         index = self.indexes[index_name]
+        if index.kind == IndexKind.BM25:
+            # the query STRINGS as they are: the index analyses them itself
+            return self.dataset.search_batch(index_name, list(queries), k=k)
         if index.kind != IndexKind.FAISS:
             raise NotImplementedError(f"{index.kind} indexes are outside the MI355X build (dense FAISS-kind only)")
         queries = np.array(queries, dtype=np.float32)
@@ -121,6 +126,12 @@ class KnowledgeBase:
         kind = IndexKind.FAISS if kind is None else IndexKind[kind]
         if index_name is None:
             index_name = column
+        if kind == IndexKind.BM25:
+            for legacy in LEGACY_INDEX_KEYS:
+                index_kwarg.pop(legacy, None)
+            self.add_or_load_bm25_index(column, index_name=index_name, **index_kwarg)
+            self.indexes[index_name] = Index(key=key, kind=kind, do_L2norm=False)
+            return
         if kind != IndexKind.FAISS:
             raise NotImplementedError(f"{kind} indexes (sparse retrieval) are outside the MI355X build")
         if index_kwarg.get("es"):
@@ -180,6 +191,32 @@ class KnowledgeBase:
                 index.save(save_path)
         register_index(self.dataset, index_name, index)
         return do_L2norm
+
+
+    def add_or_load_bm25_index(self, column, index_name=None, load=False, file=None, save_path=None, k1=None, b=None,
+                               tie_order=None, device=None, es_index_config=None, es_index_name=None, **kwargs):
+        """Builds (or loads from ``file``) the BM25 index over the TEXT column ``column`` and registers it as ``index_name``
+        (``kind: "BM25"``).  ``k1`` / ``b``: given directly, else read from a shipped config's ``es_index_config`` (the similarity
+        its ``text`` mapping names; an analyzer other than ``standard`` is refused), else Elasticsearch's defaults 1.2 / 0.75.
+        ``es_index_name`` is accepted and ignored (there is no server)."""
+        from .bm25 import MI355XBM25Index, parse_es_index_config
+        if kwargs:
+            warnings.warn(f"add_or_load_bm25_index: ignoring unknown arguments {sorted(kwargs)}")
+        if index_name is None:
+            index_name = column
+        cfg_k1, cfg_b = parse_es_index_config(es_index_config)
+        k1, b = cfg_k1 if k1 is None else k1, cfg_b if b is None else b
+        if load:
+            if file is None:
+                raise ValueError("load=True needs `file` (the path passed as save_path when the index was built)")
+            index = MI355XBM25Index.load(file, device=device, tie_order=tie_order, k1=k1, b=b)
+        else:
+            index = MI355XBM25Index(device=device, k1=k1, b=b, tie_order=tie_order)
+            index.add_documents(self.dataset, column=column)
+            if save_path is not None:
+                index.save(save_path)
+        register_index(self.dataset, index_name, index)
+        return index
 
 
 def register_index(dataset, index_name, index):
