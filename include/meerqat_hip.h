@@ -790,6 +790,75 @@ int mq_bm25_search_f32(const int64_t *ptr_dev, const int32_t *doc_dev, const flo
                        int64_t id_offset, float *D_dev, int64_t *I_dev, void *ws_dev, size_t ws_bytes, size_t budget_bytes,
                        void *stream);
 
+/* ---- face detection: MTCNN (csrc/mtcnn.hip) -- what the reference runs through facenet_pytorch on a CUDA machine
+ * (meerqat/image/face_detection.py).  The arithmetic restates the published detect_face (tests/mtcnn_restatement.py lists every
+ * restated point; parity with facenet_pytorch on the published checkpoints is UNPINNED: the package is not in this image).  Networks:
+ * fp32 FMA, fp32 accumulation.  Box geometry: separate fp32 multiplies and adds, as the elementwise tensor operations it restates.
+ * Images: the packed layout of mq_warp_affine_faces_f32 (uint8 RGB, per-image byte offset, (h, w) pairs).
+ *
+ * A box record is MQ_MTCNN_REC floats: x1, y1, x2, y2, score, reg 0..3.
+ * Packed weights (mq_mtcnn_weight_floats(net) floats): per layer, in network order, weight, bias and (where the layer has one) PReLU
+ *   slope; convolutions and heads in the published [out][in][kh][kw] / [out][in] layout, the dense layers dense4 (R-Net) and dense5
+ *   (O-Net) as [in][out] with `in` running over (c, y, x) of the map in front of them -- the published flatten order (x, y, c) is
+ *   folded into that row order by the caller.
+ * mq_mtcnn_resample_u8_f32: jobs [n_jobs][MQ_MTCNN_JOB] int64 = image, x0, y0, width, height of the rectangle (0-based; pixels outside
+ *   the image read as 0), out_w, out_h, offset (floats) of the planar [3][out_h][out_w] result in out.  Adaptive average pooling
+ *   ("area"), then (x - 127.5) * 0.0078125; a rectangle without pixels gives zeros.  A job whose result does not fit in out_floats
+ *   writes nothing and raises *overflow.  max_out_pixels: the largest out_w * out_h (sizes the launch).
+ * mq_mtcnn_pnet_f32: levels [n_levels][MQ_MTCNN_LEVEL] int64 = offset (floats) of the level's planar input, h, w, image, sub-group
+ *   (scale number), index of the level's first cell inside its image (scale-major), offset (floats) into maps, 0; level_scale
+ *   [n_levels] fp32.  Cells with prob >= threshold are appended to the image's list at [image * cap + position): rec, idx (candidate
+ *   index: first cell + row-major cell), sub.  count [n_images] receives the number of passing cells even where it exceeds cap; then
+ *   *overflow is raised and nothing is written past the list's end: grow cap and repeat.  The order of a list is unspecified
+ *   (mq_mtcnn_nms_f32 sorts).  maps (tests; may be NULL): per level [5][ho][wo] = prob, reg 0..3.  max_tiles: the largest number of
+ *   16 x 16 output tiles of a level.  n_levels <= 65535.  in_floats / maps_floats: the sizes of in and maps; a level whose input or
+ *   maps would lie outside them is not run and raises *overflow.
+ * mq_mtcnn_nms_f32: greedy NMS of n_seg segments [seg_start, seg_start + seg_count) of rec [n_total]; boxes whose score is not
+ *   > score_gt take no part; by descending score, equal scores by ascending key (NULL: position in the segment); a box is dropped
+ *   when its overlap with a kept box of the same sub (NULL: all the same) is > threshold; areas and intersections with +1.  The kept
+ *   records, keys, subs and source positions are written from seg_start on in kept order, their number to out_count.  A seg_count
+ *   that reaches past n_total, or above seg_cap (the capacity of every segment; 0: none given), is clipped, so a counter that ran
+ *   past its list never reads the next image's.  ws: mq_mtcnn_nms_workspace_bytes(n_total).
+ * mq_mtcnn_refine_f32: gathers segment g's first dst_start[g + 1] - dst_start[g] records to [dst_start[g], ...), applies the box
+ *   regression (widths with +1 under MQ_MTCNN_REFINE_PLUS_ONE), rerec under MQ_MTCNN_REFINE_REREC, then trunc + pad against image g:
+ *   out_pad [total][4] = y, ey, x, ex (1-based), valid = (ey > y - 1 && ex > x - 1), and the resampling job of the crop
+ *   (crop_size x crop_size at offset k * 3 * crop_size^2; an invalid box gets an empty rectangle).  total = dst_start[n_seg]; records
+ *   at or past out_cap are not written and raise *overflow.
+ * mq_mtcnn_rnet_f32 / mq_mtcnn_onet_f32: crops [n][3][24][24] / [n][3][48][48] -> rec[k][4] = score, rec[k][5..8] = regression
+ *   (an entry with valid[k] == 0 gets score -inf); O-Net also points [n][10] (x 0..4, y 0..4), and with MQ_MTCNN_ONET_POST maps them
+ *   to pixels (w * p + x1 - 1) and applies the regression (+1) to rec in place. */
+#define MQ_MTCNN_REC 9
+#define MQ_MTCNN_JOB 8
+#define MQ_MTCNN_LEVEL 8
+#define MQ_MTCNN_PNET 0
+#define MQ_MTCNN_RNET 1
+#define MQ_MTCNN_ONET 2
+#define MQ_MTCNN_NMS_UNION 0
+#define MQ_MTCNN_NMS_MIN 1
+#define MQ_MTCNN_REFINE_PLUS_ONE 1
+#define MQ_MTCNN_REFINE_REREC 2
+#define MQ_MTCNN_ONET_POST 1
+int mq_mtcnn_weight_floats(int net);
+int mq_mtcnn_resample_u8_f32(const uint8_t *images_dev, const int64_t *offsets_dev, const int32_t *hw_dev, int n_images,
+                             const int64_t *jobs_dev, int64_t n_jobs, int64_t max_out_pixels, float *out_dev, int64_t out_floats,
+                             int32_t *overflow_dev, void *stream);
+int mq_mtcnn_pnet_f32(const float *in_dev, int64_t in_floats, const int64_t *levels_dev, const float *level_scale_dev, int n_levels,
+                      int max_tiles, const float *weights_dev, float threshold, int n_images, int cap, float *rec_dev, int32_t *idx_dev,
+                      int32_t *sub_dev, int32_t *count_dev, int32_t *overflow_dev, float *maps_dev, int64_t maps_floats, void *stream);
+size_t mq_mtcnn_nms_workspace_bytes(int64_t n_total);
+int mq_mtcnn_nms_f32(const float *rec_dev, int64_t n_total, const int64_t *seg_start_dev, const int32_t *seg_count_dev, int n_seg,
+                     int64_t seg_cap,
+                     const int32_t *key_dev, const int32_t *sub_dev, float score_gt, float threshold, int mode, float *out_rec_dev,
+                     int32_t *out_key_dev, int32_t *out_sub_dev, int32_t *out_src_dev, int32_t *out_count_dev, void *ws_dev,
+                     size_t ws_bytes, void *stream);
+int mq_mtcnn_refine_f32(const float *in_rec_dev, const int64_t *seg_start_dev, const int64_t *dst_start_dev, int n_seg, int64_t total,
+                        const int32_t *hw_dev, int flags, int crop_size, int64_t out_cap, float *out_rec_dev, int32_t *out_img_dev,
+                        int32_t *out_pad_dev, int64_t *jobs_dev, int32_t *valid_dev, int32_t *overflow_dev, void *stream);
+int mq_mtcnn_rnet_f32(const float *crops_dev, int64_t n, const float *weights_dev, const int32_t *valid_dev, float *rec_dev,
+                      void *stream);
+int mq_mtcnn_onet_f32(const float *crops_dev, int64_t n, const float *weights_dev, const int32_t *valid_dev, float *rec_dev,
+                      float *points_dev, int flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

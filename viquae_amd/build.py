@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(CSRC, "libmeerqat_hip.so")
-SOURCES = ["knn.hip", "encoder.hip", "conv.hip", "resnet.hip", "clip_resnet.hip", "fuse.hip", "image.hip", "jpeg.hip", "diag.hip", "reader.hip", "bm25.hip", "runfmt.cpp"]
+SOURCES = ["knn.hip", "encoder.hip", "conv.hip", "resnet.hip", "clip_resnet.hip", "fuse.hip", "image.hip", "jpeg.hip", "diag.hip", "reader.hip", "bm25.hip", "mtcnn.hip", "runfmt.cpp"]
 ARCH = "gfx950"
 
 

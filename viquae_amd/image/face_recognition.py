@@ -1,5 +1,6 @@
-"""Host-side mirror of ``meerqat.image.face_recognition`` (meerqat/image/face_recognition.py): ArcFace embeddings of the faces an
-upstream detector (``meerqat.image.face_detection``, out of scope) left as 5-point ``face_landmarks`` in the dataset.
+"""Host-side mirror of ``meerqat.image.face_recognition`` (meerqat/image/face_recognition.py): ArcFace embeddings of the faces the
+detector (:mod:`viquae_amd.image.face_detection`, MTCNN on the device, or the reference's ``meerqat.image.face_detection``) left as
+5-point ``face_landmarks`` in the dataset.
 
 Same names and call shapes as the reference for the hot-path surface:
 
