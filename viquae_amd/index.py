@@ -10,6 +10,7 @@ It subclasses ``datasets.search.BaseIndex`` so that ``Dataset.search_batch`` /
 All arithmetic happens in libmeerqat_hip.so (csrc/knn.hip) through the C ABI; torch only owns the
 device buffers and the stream.  No CPU fallback.
 """
+import contextlib
 import os
 import struct
 from pathlib import PurePath
@@ -111,7 +112,97 @@ def _resolve_device(device):
                     "Please pass in either nothing, a positive int, a negative int, or a list of positive ints.")
 
 
-class MI355XFlatIndex(BaseIndex):
+def whole_panel_blocks(blocks):
+    """Re-cuts an iterable of [n, d] blocks so that every block yielded but the last holds a multiple of 64 rows (the C ABI
+    packs whole 64-row panels; add() re-packs an open one).  A block that is whole already is passed on as it is, uncopied."""
+    pend = None
+    for block in blocks:
+        if pend is not None:
+            block, pend = np.concatenate([pend, block]), None
+        full = block.shape[0] // 64 * 64
+        if full < block.shape[0]:
+            pend = block[full:] if full else block
+            block = block[:full]
+        if full:
+            yield block
+    if pend is not None:
+        yield pend
+
+
+def check_search_args(queries, k, d=None):
+    """The argument checks of every ``search_device``: a [nq, d] query tensor (``d``: the index's, when known), 1 <= k <= MAX_K."""
+    if d is not None and (queries.dim() != 2 or queries.shape[1] != d):
+        raise ValueError(f"Shape of query must be 2D with {d} columns, got {tuple(queries.shape)}")
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if k > MAX_K:
+        raise NotImplementedError(f"k={k} > {MAX_K} (MQ_KNN_MAX_K, FAISS-GPU's own limit)")
+
+
+class HostBoundaryIndex(BaseIndex):
+    """``search`` / ``search_batch`` (numpy in, numpy out) of every flat index, in terms of ``self._query_device()`` (where the
+    queries go) and ``self.search_device(q, k)`` (device tensors in and out)."""
+
+    def __init__(self):
+        self._io = None  # (q pinned, q on the device, D pinned, I pinned, the device): staging of search_batch
+
+    def __reduce__(self):
+        # Like a FAISS GPU index: device-resident, not picklable.  It also keeps `datasets` from hashing the whole shard
+        # (a device -> host copy of every buffer, ~9 s at 1.5M x 768) when it fingerprints a Dataset.map call whose function
+        # captures the index (Searcher -> KnowledgeBase -> index): on this error it falls back to a random fingerprint.
+        raise TypeError(f"{type(self).__name__} lives in HBM and cannot be pickled: use save() / load_rows()")
+
+    def search_batch(self, queries, k: int = 10, **kwargs) -> BatchedSearchResults:
+        """FaissIndex.search_batch (datasets/search.py:369-385): numpy [nq,d] -> (scores f32 [nq,k],
+        indices int [nq,k]), best first, -1 for unfilled slots."""
+        import torch
+        queries = np.asarray(queries)
+        if len(queries.shape) != 2:
+            raise ValueError("Shape of query must be 2D")
+        dev = self._query_device()
+        nq, d = queries.shape
+        on_gpu = torch.device(dev).type == "cuda"  # (the gloo CPU tests serve the local index from the oracle: plain copies there)
+        if not on_gpu or nq == 0 or nq > _PINNED_IO_MAX_QUERIES:
+            q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
+            D, I = self.search_device(q, k)
+            if on_gpu:
+                torch.cuda.current_stream(dev).synchronize()
+            return BatchedSearchResults(D.cpu().numpy(), I.cpu().numpy().astype(int))
+        # Host boundary of one batch (the reference sends 256 queries at a time): page-locked staging buffers kept by the
+        # index, asynchronous copies on the search stream, ONE synchronisation -- instead of three blocking pageable copies.
+        q_pin, q_dev, D_pin, I_pin, _ = self._host_io(nq, d, k, dev)
+        np.copyto(q_pin[:nq].numpy(), queries, casting="same_kind" if queries.dtype.kind == "f" else "unsafe")
+        with torch.cuda.device(dev):
+            q_dev[:nq].copy_(q_pin[:nq], non_blocking=True)
+            D, I = self.search_device(q_dev[:nq], k)
+            D_pin[:nq].copy_(D, non_blocking=True)
+            I_pin[:nq].copy_(I, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return BatchedSearchResults(D_pin[:nq].numpy().copy(), I_pin[:nq].numpy().astype(int))
+
+    def _host_io(self, nq, d, k, dev):
+        """Page-locked (q, D, I) staging + the device query buffer, grown geometrically and reused across calls of one
+        (d, k, device)."""
+        import torch
+        io = self._io
+        if io is None or io[0].shape[0] < nq or io[0].shape[1] != d or io[2].shape[1] != k or io[4] != dev:
+            cap = max(256, 1 << (int(nq) - 1).bit_length())
+            io = self._io = (torch.empty((cap, d), dtype=torch.float32).pin_memory(),
+                             torch.empty((cap, d), dtype=torch.float32, device=dev),
+                             torch.empty((cap, k), dtype=torch.float32).pin_memory(),
+                             torch.empty((cap, k), dtype=torch.int64).pin_memory(), dev)
+        return io
+
+    def search(self, query, k: int = 10, **kwargs) -> SearchResults:
+        """FaissIndex.search (datasets/search.py:349-367)."""
+        query = np.asarray(query)
+        if len(query.shape) != 1 and (len(query.shape) != 2 or query.shape[0] != 1):
+            raise ValueError("Shape of query is incorrect, it has to be either a 1D array or 2D (1, N)")
+        scores, indices = self.search_batch(query.reshape(1, -1), k)
+        return SearchResults(scores[0], indices[0].astype(int))
+
+
+class MI355XFlatIndex(HostBoundaryIndex):
     """Exact IP / L2 index over an fp32 matrix held in HBM in the kernel's panel layout."""
 
     def __init__(self, device: Optional[Union[int, list]] = None, string_factory: Optional[str] = None,
@@ -119,6 +210,7 @@ class MI355XFlatIndex(BaseIndex):
                  keep_panel: Optional[bool] = None, tie_order: Optional[str] = None, l2norm_form: Optional[str] = None):
         if custom_index is not None:
             raise ValueError("custom_index is a FAISS object; MI355XFlatIndex builds its own index")
+        super().__init__()
         self.device = device
         self.string_factory = string_factory
         # FAISS: IndexFlat(d) and index_factory(d, "Flat") default to METRIC_L2 when no metric is given
@@ -126,6 +218,7 @@ class MI355XFlatIndex(BaseIndex):
         if self.metric_type not in (METRIC_INNER_PRODUCT, METRIC_L2):
             raise ValueError(f"Unsupported metric_type {metric_type} (0 = inner product, 1 = L2)")
         self.do_l2norm = parse_string_factory(string_factory)
+        self._l2norm_form_given = l2norm_form  # None: load_rows may choose FAISS's form for a stored "L2norm,Flat" index
         # Arithmetic of the "L2norm," prefix (include/meerqat_hip.h): "numpy" = x / sqrt(sum x^2), the reference's L2norm()
         # (meerqat/ir/search.py:43-46) and what its GPU work-around applies to the KB column when `device` is given (:238-244);
         # "faiss" = FAISS's NormalizationTransform (x * float(1.0 / sqrt(sum x^2)), rows of norm 0 left untouched), what
@@ -149,8 +242,12 @@ class MI355XFlatIndex(BaseIndex):
         self._packed = None  # torch.float32 [padded_rows * padded_dim]
         self._sqnorm = None  # torch.float32 [padded_rows]
         self._capacity = 0
-        self._ws = None
-        self._torch_device = None
+        self._torch_device = None  # resolved from `device` at the first add or search (_query_device)
+        # search state: the workspace of the C-ABI calls (assignable: the next search reuses it when large enough), the second
+        # one + the stream of the pipelined search (MQ_KNN_TAIL_OVERLAP=1), and what screen_stats reads back: the workspace and
+        # the query count of the LAST C-ABI call
+        self._ws = self._ws2 = self._tail_stream = None
+        self._last_ws = self._last_call_nq = None
         # screened search (bf16 screening + exact re-scoring, same results, csrc/knn_screen.inc): inner-product
         # indexes only; costs 1.5x the shard's HBM footprint.  MQ_KNN_SCREEN=0/1 overrides the default.
         if screen is None:
@@ -171,18 +268,16 @@ class MI355XFlatIndex(BaseIndex):
         self._screen_metric = self.metric_type   # what the mq_knn_screen_* entries are told: METRIC_IP_CENTRED (2) when the
         #                        queries are centred as well (decided at the first add, _prepare_screen)
 
-    def __reduce__(self):
-        # Like a FAISS GPU index: device-resident, not picklable.  It also keeps `datasets` from hashing the whole shard
-        # (a device -> host copy of every buffer, ~9 s at 1.5M x 768) when it fingerprints a Dataset.map call whose function
-        # captures the index (Searcher -> KnowledgeBase -> index): on this error it falls back to a random fingerprint.
-        raise TypeError(f"{type(self).__name__} lives in HBM and cannot be pickled: use save() / load()")
-
     # ------------------------------------------------------------------ construction
+    def _query_device(self):
+        if self._torch_device is None:
+            self._torch_device = _resolve_device(self.device)
+        return self._torch_device
+
     def _ensure_capacity(self, n_total, d, exact=True):
         import torch
         lib = _lib.load()
-        if self._torch_device is None:
-            self._torch_device = _resolve_device(self.device)
+        self._query_device()
         if self.d is None:
             self.d = int(d)
         elif self.d != int(d):
@@ -214,75 +309,61 @@ class MI355XFlatIndex(BaseIndex):
         """Append rows (numpy [n,d] or a CUDA torch tensor), any number at a time like ``faiss.Index.add``.  The C ABI
         packs whole 64-row panels: when the rows already stored end inside a panel, that panel's stored rows are read
         back and re-packed together with the first new rows (bit-identical: they are stored after the "L2norm,"
-        transform and are not transformed twice)."""
+        transform and are not transformed twice).  A screened index without a panel copy has no open panel to finish."""
         import torch
         lib = _lib.load()
-        if isinstance(vecs, torch.Tensor):
-            if vecs.dim() != 2:
-                raise ValueError("expected a 2-D matrix of vectors")
-            n, d = vecs.shape
-        else:
+        if not isinstance(vecs, torch.Tensor):
             vecs = np.asarray(vecs, dtype=np.float32)
-            if vecs.ndim != 2:
-                raise ValueError("expected a 2-D matrix of vectors")
-            n, d = vecs.shape
+        if vecs.ndim != 2:
+            raise ValueError("expected a 2-D matrix of vectors")
+        n, d = vecs.shape
         if n == 0:
             return
         if self.screen and self._xmax2 is None:
             self._prepare_screen(vecs[:_UPLOAD_ROWS], d)  # centre + screen metric: BEFORE the bf16 copy is sized
         self._ensure_capacity(max(self.ntotal + n, total_hint or 0), d, exact=bool(total_hint))
         stream = torch.cuda.current_stream(self._torch_device).cuda_stream
-        if not self.keep_panel:
-            return self._add_rows_only(vecs, n, stream)
         first = 0
-        if self.ntotal % 64 != 0:
-            # finish the open panel: stored tail rows (already transformed) + the first new rows (transformed here)
-            floor = self.ntotal // 64 * 64
-            first = min(n, 64 - (self.ntotal - floor))
-            with torch.cuda.device(self._torch_device):
+        with torch.cuda.device(self._torch_device):
+            if self.keep_panel and self.ntotal % 64 != 0:
+                # finish the open panel: stored tail rows (already transformed) + the first new rows (transformed here, in a
+                # private copy: _upload hands a device tensor of the caller's back as it is)
+                floor = self.ntotal // 64 * 64
+                first = min(n, 64 - (self.ntotal - floor))
                 tail = torch.empty((self.ntotal - floor, self.d), dtype=torch.float32, device=self._torch_device)
                 _lib.check(lib.mq_unpack_rows_f32(self._packed.data_ptr(), self._capacity, self.d, floor, tail.shape[0],
                                                   tail.data_ptr(), stream), "mq_unpack_rows_f32")
-                head = vecs[:first]
-                head = (head if isinstance(head, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(head)))
-                head = head.to(device=self._torch_device, dtype=torch.float32).contiguous().clone()
+                head = self._upload(vecs[:first]).clone()
                 if self.do_l2norm:
                     _lib.check(lib.mq_l2norm_rows_form_f32(head.data_ptr(), head.shape[0], self.d, L2NORM_FORMS[self.l2norm_form], stream),
                                "mq_l2norm_rows_form_f32")
-                blk = torch.cat([tail, head]).contiguous()
-                _lib.check(lib.mq_pack_rows_f32(blk.data_ptr(), blk.shape[0], self.d, floor, 0, self._packed.data_ptr(),
-                                                self._capacity, self._sqnorm.data_ptr(), stream), "mq_pack_rows_f32")
-                if self.screen:
-                    _lib.check(lib.mq_knn_screen_prepare(self._packed.data_ptr(), self._sqnorm.data_ptr(), self._capacity, self.d,
-                                                         self._screen_metric, floor, blk.shape[0], self._rowmajor.data_ptr(),
-                                                         self._bf16.data_ptr(), self._xmax2.data_ptr(),
-                                                         self._center.data_ptr() if self._center is not None else None, stream),
-                               "mq_knn_screen_prepare")
-                self.ntotal = floor + blk.shape[0]
+                self._store_rows(torch.cat([tail, head]).contiguous(), floor, 0, stream)
                 torch.cuda.current_stream(self._torch_device).synchronize()
-        with torch.cuda.device(self._torch_device):
             for i in range(first, n, _UPLOAD_ROWS):
-                part = vecs[i:i + _UPLOAD_ROWS]
-                if isinstance(part, torch.Tensor):
-                    dev = part.to(device=self._torch_device, dtype=torch.float32).contiguous()
-                else:
-                    part = np.ascontiguousarray(part)
-                    if not part.flags.writeable:
-                        part = part.copy()
-                    dev = torch.from_numpy(part).to(self._torch_device, non_blocking=False)
-                _lib.check(lib.mq_pack_rows_f32(dev.data_ptr(), dev.shape[0], self.d, self.ntotal, self._l2norm_arg(),
-                                                self._packed.data_ptr(), self._capacity, self._sqnorm.data_ptr(),
-                                                stream), "mq_pack_rows_f32")
-                if self.screen:
-                    _lib.check(lib.mq_knn_screen_prepare(self._packed.data_ptr(), self._sqnorm.data_ptr(), self._capacity, self.d,
-                                                         self._screen_metric, self.ntotal, dev.shape[0], self._rowmajor.data_ptr(),
-                                                         self._bf16.data_ptr(), self._xmax2.data_ptr(),
-                                                         self._center.data_ptr() if self._center is not None else None, stream),
-                               "mq_knn_screen_prepare")
-                self.ntotal += dev.shape[0]
-                # `dev` goes back to torch's caching allocator while the kernels may still be queued: they run on torch's
-                # current stream, and the allocator only hands the block to later work of that same stream
+                # the uploaded block goes back to torch's caching allocator while the kernels may still be queued: they run on
+                # torch's current stream, and the allocator only hands the block to later work of that same stream
+                self._store_rows(self._upload(vecs[i:i + _UPLOAD_ROWS]), self.ntotal, self._l2norm_arg(), stream)
             torch.cuda.current_stream(self._torch_device).synchronize()
+
+    def _store_rows(self, dev, row0, l2norm, stream):
+        """Stores the device rows ``dev`` from row ``row0`` on (the index's last rows then).  With a panel copy (``row0`` a
+        multiple of 64): the packing kernel's "L2norm," transform and ||x||^2, then the screening copies from the panel.
+        Without one (a screened index): the same arithmetic straight into the row-major store, at any row offset, then the bf16
+        copy."""
+        lib = _lib.load()
+        center = self._center.data_ptr() if self._center is not None else None
+        if not self.keep_panel:
+            _lib.check(lib.mq_knn_screen_add_rows_f32(
+                dev.data_ptr(), dev.shape[0], self.d, row0, l2norm, self._screen_metric, self._capacity, self._sqnorm.data_ptr(),
+                self._rowmajor.data_ptr(), self._bf16.data_ptr(), self._xmax2.data_ptr(), center, stream), "mq_knn_screen_add_rows_f32")
+        else:
+            _lib.check(lib.mq_pack_rows_f32(dev.data_ptr(), dev.shape[0], self.d, row0, l2norm, self._packed.data_ptr(),
+                                            self._capacity, self._sqnorm.data_ptr(), stream), "mq_pack_rows_f32")
+            if self.screen:
+                _lib.check(lib.mq_knn_screen_prepare(
+                    self._packed.data_ptr(), self._sqnorm.data_ptr(), self._capacity, self.d, self._screen_metric, row0, dev.shape[0],
+                    self._rowmajor.data_ptr(), self._bf16.data_ptr(), self._xmax2.data_ptr(), center, stream), "mq_knn_screen_prepare")
+        self.ntotal = row0 + dev.shape[0]
 
     def _upload(self, part):
         import torch
@@ -292,21 +373,6 @@ class MI355XFlatIndex(BaseIndex):
         if not part.flags.writeable:
             part = part.copy()
         return torch.from_numpy(part).to(self._torch_device, non_blocking=False)
-
-    def _add_rows_only(self, vecs, n, stream):
-        """add() of a screened index without a panel copy: the rows go straight to the row-major store (any row offset, no
-        open-panel bookkeeping) with the "L2norm," transform and ||x||^2 of the packing kernel, then to the bf16 copy."""
-        import torch
-        lib = _lib.load()
-        with torch.cuda.device(self._torch_device):
-            for i in range(0, n, _UPLOAD_ROWS):
-                dev = self._upload(vecs[i:i + _UPLOAD_ROWS])
-                _lib.check(lib.mq_knn_screen_add_rows_f32(
-                    dev.data_ptr(), dev.shape[0], self.d, self.ntotal, self._l2norm_arg(), self._screen_metric, self._capacity,
-                    self._sqnorm.data_ptr(), self._rowmajor.data_ptr(), self._bf16.data_ptr(), self._xmax2.data_ptr(),
-                    self._center.data_ptr() if self._center is not None else None, stream), "mq_knn_screen_add_rows_f32")
-                self.ntotal += dev.shape[0]  # `dev` is released stream-ordered (see add())
-            torch.cuda.current_stream(self._torch_device).synchronize()
 
     def _prepare_screen(self, first_rows, d):
         """First add of a screened index: the centre of the bf16 copy (``_choose_center``) and whether the QUERIES are centred as
@@ -319,8 +385,7 @@ class MI355XFlatIndex(BaseIndex):
         13th K block would cost the one-query-tile search its streaming kernel (at d = 768 the two columns sit alone in that block
         and the streaming kernel takes the row term as fp32, round 6).  MQ_KNN_CENTER_QUERIES=0 / 1 overrides."""
         import torch
-        if self._torch_device is None:
-            self._torch_device = _resolve_device(self.device)
+        self._query_device()
         dev = self._upload(first_rows)
         center = self._choose_center(dev)
         self._screen_metric = self.metric_type
@@ -386,38 +451,16 @@ class MI355XFlatIndex(BaseIndex):
                 raise ValueError("expected a 2-D matrix of vectors")
             self.add(mat, total_hint=self.ntotal + mat.shape[0])
             return
-        n_total = len(vectors)
-        added = 0
-        for block in iter_arrow_column(vectors, column):
-            # keep every add but the last a multiple of 64 rows
-            self._pending = block if getattr(self, "_pending", None) is None else np.concatenate([self._pending, block])
-            full = (self._pending.shape[0] // 64) * 64
-            if full:
-                self.add(self._pending[:full], total_hint=self.ntotal - added + n_total)
-                added += full
-                self._pending = self._pending[full:]
-        if getattr(self, "_pending", None) is not None and self._pending.shape[0]:
-            self.add(self._pending, total_hint=self.ntotal - added + n_total)
-        self._pending = None
+        total = self.ntotal + len(vectors)
+        for block in whole_panel_blocks(iter_arrow_column(vectors, column)):
+            self.add(block, total_hint=total)
 
     # ------------------------------------------------------------------ search
-    def _workspace(self, nbytes):
+    def _fit_workspace(self, ws, nbytes):
+        """``ws`` when it holds ``nbytes``, a new workspace otherwise."""
         import torch
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self._torch_device)
-        self._last_ws = self._ws
-        return self._ws
-
-    def _second_workspace(self, nbytes):
-        """The workspace of the odd chunks of a pipelined search (chunk i's second half reads its workspace while chunk i+1's
-        scan fills the other one) + the stream those second halves run on."""
-        import torch
-        ws = getattr(self, "_ws2", None)
         if ws is None or ws.numel() < nbytes:
-            self._ws2 = ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self._torch_device)
-        if getattr(self, "_tail_stream", None) is None:
-            self._tail_stream = torch.cuda.Stream(device=self._torch_device)
-        self._last_ws = ws
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self._torch_device)
         return ws
 
     def search_device(self, queries, k, out=None):
@@ -426,17 +469,10 @@ class MI355XFlatIndex(BaseIndex):
         ``out`` = (D, I) preallocated contiguous CUDA tensors to write into (e.g. views of a shard record)."""
         import torch
         lib = _lib.load()
-        if self._sqnorm is None:
+        if self._sqnorm is None or self.ntotal == 0:
             raise ValueError("the index is empty: call add_vectors first")
-        if queries.dim() != 2 or queries.shape[1] != self.d:
-            raise ValueError(f"Shape of query must be 2D with {self.d} columns, got {tuple(queries.shape)}")
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        if k > MAX_K:
-            raise NotImplementedError(f"k={k} > {MAX_K} (MQ_KNN_MAX_K, FAISS-GPU's own limit)")
+        check_search_args(queries, k, self.d)
         nq = queries.shape[0]
-        if self.ntotal == 0:
-            raise ValueError("the index is empty: call add_vectors first")
         queries = queries.to(dtype=torch.float32).contiguous()
         if out is not None:
             D, I = out
@@ -452,22 +488,15 @@ class MI355XFlatIndex(BaseIndex):
             chunk = _SCREEN_QUERY_CHUNK if self.screen else _QUERY_CHUNK
             pieces = query_chunks(nq, chunk)
             if self.screen and len(pieces) > 1 and os.environ.get("MQ_KNN_TAIL_OVERLAP", "0") == "1":
-                self._search_chunks_pipelined(lib, queries, pieces, k, D, I)
+                self._search_chunks_pipelined(queries, pieces, k, D, I)
                 return D, I
+            flags = self._search_flags()
             for s, e in pieces:
-                q = queries[s:e]
-                self._last_call_nq = e - s  # screen_stats reads the workspace geometry of the LAST C-ABI call
+                q, Dq, Iq = queries[s:e], D[s:e], I[s:e]
                 nb = int(lib.mq_knn_workspace_bytes_metric(self.ntotal, self.d, q.shape[0], k, self._screen_metric if self.screen else self.metric_type))
-                ws = self._workspace(nb)
-                Dq, Iq = D[s:e], I[s:e]
-                flags = self._search_flags()
+                ws = self._ws = self._fit_workspace(self._ws, nb)
                 if self.screen:
-                    _lib.check(lib.mq_knn_search_screened_f32(
-                        self._packed.data_ptr() if self._packed is not None else None, self._sqnorm.data_ptr(), self._rowmajor.data_ptr(), self._bf16.data_ptr(),
-                        self._xmax2.data_ptr(), self.ntotal, self.d, q.data_ptr(), q.shape[0], k, self._screen_metric,
-                        flags,
-                        self.id_offset, Dq.data_ptr(), Iq.data_ptr(), ws.data_ptr(), ws.numel(), stream, None, None),
-                        "mq_knn_search_screened_f32")
+                    self._search_screened(q, k, (Dq, Iq), ws, flags, stream)
                 else:
                     _lib.check(lib.mq_knn_search_f32(self._packed.data_ptr(), self._sqnorm.data_ptr(), self.ntotal, self.d,
                                                      q.data_ptr(), q.shape[0], k, self.metric_type, flags,
@@ -475,13 +504,23 @@ class MI355XFlatIndex(BaseIndex):
                                                      stream), "mq_knn_search_f32")
         return D, I
 
+    def _search_screened(self, q, k, out, ws, flags, stream):
+        """THE call of mq_knn_search_screened_f32: one chunk ``q`` (<= 4096 queries) into out = (D, I) with workspace ``ws`` on
+        the raw stream handle ``stream``.  screen_stats reads the workspace geometry of the LAST such call."""
+        self._last_call_nq, self._last_ws = q.shape[0], ws
+        _lib.check(_lib.load().mq_knn_search_screened_f32(
+            self._packed.data_ptr() if self._packed is not None else None, self._sqnorm.data_ptr(), self._rowmajor.data_ptr(),
+            self._bf16.data_ptr(), self._xmax2.data_ptr(), self.ntotal, self.d, q.data_ptr(), q.shape[0], k, self._screen_metric,
+            flags, self.id_offset, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws.numel(), stream, None, None),
+            "mq_knn_search_screened_f32")
+
     def _search_flags(self):
         flags = (FLAG_L2NORM_QUERIES if self.do_l2norm else 0) | (FLAG_TIE_ID_DESC if self.tie_order == "id_desc" else 0)
         if self.do_l2norm and self.l2norm_form == "faiss":
             flags |= FLAG_L2NORM_FAISS
         return flags
 
-    def _search_chunks_pipelined(self, lib, queries, pieces, k, D, I):
+    def _search_chunks_pipelined(self, queries, pieces, k, D, I):
         """A screened search of several query chunks: the scans run back to back on the caller's stream, and what follows
         the scan of chunk i (candidate selection, exact re-scoring, exact top-k, recomputation of flagged tiles: about a
         tenth of a chunk's time, mostly latency-bound launches of one workgroup per query) runs on a second stream under the
@@ -511,72 +550,19 @@ class MI355XFlatIndex(BaseIndex):
             main.wait_event(ev)
 
     def pipeline_workspaces(self, nq, k):
-        """-> ((workspace of even chunks, workspace of odd chunks), the stream second halves run on) for chunks of <= nq queries."""
+        """-> ((workspace of even chunks, workspace of odd chunks), the stream second halves run on) for chunks of <= nq queries:
+        chunk i's second half reads its workspace while chunk i+1's scan fills the other one."""
+        import torch
         nb = int(_lib.load().mq_knn_workspace_bytes_metric(self.ntotal, self.d, int(nq), k, self._screen_metric))
-        return (self._workspace(nb), self._second_workspace(nb)), self._tail_stream
+        self._ws, self._ws2 = self._fit_workspace(self._ws, nb), self._fit_workspace(self._ws2, nb)
+        if self._tail_stream is None:
+            self._tail_stream = torch.cuda.Stream(device=self._torch_device)
+        return (self._ws, self._ws2), self._tail_stream
 
     def search_phase(self, q, k, out, ws, phase, stream):
         """One half (FLAG_PHASE_FRONT / FLAG_PHASE_TAIL) of the screened search of ONE chunk (<= 4096 queries) on ``stream``;
         both halves take the same q, out = (D, I) and workspace, and the caller orders TAIL after FRONT."""
-        self._last_call_nq, self._last_ws = q.shape[0], ws
-        _lib.check(_lib.load().mq_knn_search_screened_f32(
-            self._packed.data_ptr() if self._packed is not None else None, self._sqnorm.data_ptr(), self._rowmajor.data_ptr(),
-            self._bf16.data_ptr(), self._xmax2.data_ptr(), self.ntotal, self.d, q.data_ptr(), q.shape[0], k, self._screen_metric,
-            self._search_flags() | phase, self.id_offset, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws.numel(),
-            stream.cuda_stream, None, None), "mq_knn_search_screened_f32")
-
-    def search_batch(self, queries, k: int = 10, **kwargs) -> BatchedSearchResults:
-        """FaissIndex.search_batch (datasets/search.py:369-385): numpy [nq,d] -> (scores f32 [nq,k],
-        indices int [nq,k]), best first, -1 for unfilled slots."""
-        import torch
-        queries = np.asarray(queries)
-        if len(queries.shape) != 2:
-            raise ValueError("Shape of query must be 2D")
-        if self._torch_device is None:
-            self._torch_device = _resolve_device(self.device)
-        nq = queries.shape[0]
-        if nq == 0 or nq > _PINNED_IO_MAX_QUERIES:
-            q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(self._torch_device)
-            D, I = self.search_device(q, k)
-            torch.cuda.current_stream(self._torch_device).synchronize()
-            return BatchedSearchResults(D.cpu().numpy(), I.cpu().numpy().astype(int))
-        # Host boundary of one batch (the reference sends 256 queries at a time): page-locked staging buffers kept by the
-        # index, asynchronous copies on the search stream, ONE synchronisation -- instead of three blocking pageable copies.
-        q_pin, q_dev, D_pin, I_pin = self._host_io(nq, queries.shape[1], k)
-        np.copyto(q_pin[:nq].numpy(), queries, casting="same_kind" if queries.dtype.kind == "f" else "unsafe")
-        stream = torch.cuda.current_stream(self._torch_device)
-        with torch.cuda.device(self._torch_device):
-            q_dev[:nq].copy_(q_pin[:nq], non_blocking=True)
-            D, I = self.search_device(q_dev[:nq], k)
-            D_pin[:nq].copy_(D, non_blocking=True)
-            I_pin[:nq].copy_(I, non_blocking=True)
-        stream.synchronize()
-        return BatchedSearchResults(D_pin[:nq].numpy().copy(), I_pin[:nq].numpy().astype(int))
-
-    def _host_io(self, nq, d, k):
-        """Page-locked (q, D, I) staging + the device query buffer, grown geometrically and reused across calls."""
-        import torch
-        io = getattr(self, "_io", None)
-        if io is None or io[0].shape[0] < nq or io[0].shape[1] != d or io[2].shape[1] != k:
-            cap = max(256, 1 << (int(nq) - 1).bit_length())
-            io = (torch.empty((cap, d), dtype=torch.float32).pin_memory(),
-                  torch.empty((cap, d), dtype=torch.float32, device=self._torch_device),
-                  torch.empty((cap, k), dtype=torch.float32).pin_memory(),
-                  torch.empty((cap, k), dtype=torch.int64).pin_memory())
-            self._io = io
-        return io
-
-    def search(self, query, k: int = 10, **kwargs) -> SearchResults:
-        """FaissIndex.search (datasets/search.py:349-367)."""
-        query = np.asarray(query)
-        if len(query.shape) != 1 and (len(query.shape) != 2 or query.shape[0] != 1):
-            raise ValueError("Shape of query is incorrect, it has to be either a 1D array or 2D (1, N)")
-        scores, indices = self.search_batch(query.reshape(1, -1), k)
-        return SearchResults(scores[0], indices[0].astype(int))
-
-    def _stats_workspace(self):
-        ws = getattr(self, "_last_ws", None)
-        return self._ws if ws is None else ws
+        self._search_screened(q, k, out, ws, self._search_flags() | phase, stream.cuda_stream)
 
     def scan_kind(self, nq, k):
         """Which screening scan serves a ``search_device`` call of ``nq`` queries: "tile" (256 x 256 tiles), "stream" (one query
@@ -588,20 +574,22 @@ class MI355XFlatIndex(BaseIndex):
             raise ValueError(f"mq_knn_screen_scan_kind: invalid arguments (status {kind})")
         return ("none", "tile", "stream")[kind]
 
-    # ------------------------------------------------------------------ persistence
     def screen_stats(self, nq, k):
         """(query tiles recomputed exactly, candidates re-scored, max per query, ...) of the LAST C-ABI call of the last
         screened search (a search of more than 4096 queries is several calls)."""
         import ctypes
+        import torch
         lib = _lib.load()
         if nq > _SCREEN_QUERY_CHUNK:
             # the size of the last piece search_device cut (query_chunks moves 40 queries into a short tail)
-            nq = getattr(self, "_last_call_nq", None) or query_chunks(nq, _SCREEN_QUERY_CHUNK)[-1][1] - query_chunks(nq, _SCREEN_QUERY_CHUNK)[-1][0]
+            nq = self._last_call_nq or query_chunks(nq, _SCREEN_QUERY_CHUNK)[-1][1] - query_chunks(nq, _SCREEN_QUERY_CHUNK)[-1][0]
         out = (ctypes.c_int64 * 8)()
-        _lib.check(lib.mq_knn_screen_stats(self.ntotal, self.d, nq, k, self._stats_workspace().data_ptr(), out,
-                                           __import__("torch").cuda.current_stream(self._torch_device).cuda_stream))
+        ws = self._ws if self._last_ws is None else self._last_ws
+        _lib.check(lib.mq_knn_screen_stats(self.ntotal, self.d, nq, k, ws.data_ptr(), out,
+                                           torch.cuda.current_stream(self._torch_device).cuda_stream))
         return tuple(int(x) for x in out)
 
+    # ------------------------------------------------------------------ persistence
     def reconstruct_n(self, start=0, n=None):
         """Stored rows (after any L2norm transform) as numpy [n,d]."""
         import torch
@@ -629,28 +617,43 @@ class MI355XFlatIndex(BaseIndex):
             f.write(index_file_header(self.ntotal, self.d or 0, self.metric_type, self.do_l2norm, index_file_format(file, format)))
             f.write(rows.tobytes())
 
-    @classmethod
-    def load(cls, file: Union[str, PurePath], device=None, storage_options: Optional[dict] = None, tie_order=None, l2norm_form=None):
-        """FaissIndex.load (datasets/search.py:399-416).  Reads this class's own files and the FAISS files
-        the reference's ``save_path`` / ``dataset.save_faiss_index`` wrote for the factories it ships
-        (IndexFlat, and IndexPreTransform(NormalizationTransform, IndexFlat) for "L2norm,Flat")."""
+    @contextlib.contextmanager
+    def _stored_rows(self, metric, l2norm):
+        """Inside: this index has the metric of an index FILE and adds rows as they are -- the file's rows were stored after the
+        "L2norm," transform and are not normalised twice.  Afterwards: the file's transform, applied to the QUERIES, in the
+        arithmetic asked for at construction, else MQ_KNN_L2NORM_FORM's, else FAISS's: a stored "L2norm,Flat" index is the
+        reference's CPU-FAISS object (meerqat/ir/search.py:247-248 saves, :235 loads it), whose queries go through FAISS's own
+        NormalizationTransform.  (FaissIndex.load reads metric and transform from the FILE, datasets/search.py:399-416: a load
+        config may omit string_factory / metric_type.)"""
+        self.metric_type = self._screen_metric = int(metric)
+        self.string_factory = "L2norm,Flat" if l2norm else "Flat"
+        self.do_l2norm = False
+        try:
+            yield
+        finally:
+            self.do_l2norm = bool(l2norm)
+            if l2norm:
+                self.l2norm_form = self._l2norm_form_given or os.environ.get("MQ_KNN_L2NORM_FORM", "faiss")
+
+    def load_rows(self, file):
+        """Fill this (empty) index from a file: this class's own format or the FAISS files the reference's ``save_path`` /
+        ``dataset.save_faiss_index`` wrote for the factories it ships (IndexFlat, and IndexPreTransform(NormalizationTransform,
+        IndexFlat) for "L2norm,Flat").  Metric and the "L2norm," transform come from the file."""
         path = os.fspath(file)
         n, d, metric, l2norm, data_off = read_index_file_header(path)
-        if l2norm and l2norm_form is None:
-            # a stored "L2norm,Flat" index is the reference's CPU-FAISS object (meerqat/ir/search.py:247-248 saves, :235 loads it):
-            # its queries go through FAISS's own NormalizationTransform
-            l2norm_form = os.environ.get("MQ_KNN_L2NORM_FORM", "faiss")
-        idx = cls(device=device, string_factory="L2norm,Flat" if l2norm else "Flat", metric_type=metric, tie_order=tie_order,
-                  l2norm_form=l2norm_form)
-        if n:
-            rows = np.fromfile(path, dtype=np.float32, count=n * d, offset=data_off).reshape(n, d)
-            # rows were stored after normalisation: do not normalise twice on load
-            idx.do_l2norm = False
-            idx.add(rows, total_hint=n)
-            idx.do_l2norm = bool(l2norm)
-        else:
-            idx.d = d or None
-        return idx
+        if self.ntotal:
+            raise ValueError("load_rows fills an EMPTY index")
+        with self._stored_rows(metric, l2norm):
+            if n:
+                self.add(np.fromfile(path, dtype=np.float32, count=n * d, offset=data_off).reshape(n, d), total_hint=n)
+            else:
+                self.d = d or None
+        return self
+
+    @classmethod
+    def load(cls, file: Union[str, PurePath], device=None, storage_options: Optional[dict] = None, tie_order=None, l2norm_form=None):
+        """FaissIndex.load (datasets/search.py:399-416): a new index + :meth:`load_rows`."""
+        return cls(device=device, tie_order=tie_order, l2norm_form=l2norm_form).load_rows(file)
 
 
 def index_file_format(path, format=None):

@@ -23,7 +23,6 @@ import warnings
 
 import numpy as np
 
-from ..index import MI355XFlatIndex
 
 # keys that every shipped experiments/ir/**/config.json still carries but that the current
 # reference code path no longer consumes: accepted and ignored
@@ -165,26 +164,19 @@ class KnowledgeBase:
         do_L2norm = string_factory is not None and "L2norm" in string_factory
         # which index class serves `device` (one GPU, all GPUs of this process, or this rank's shard of a
         # torch.distributed job): viquae_amd.sharded.make_flat_index
-        from ..sharded import ShardedFlatIndex, make_flat_index
+        from ..sharded import make_flat_index
         if l2norm_form is None and do_L2norm and not load:
             # only a BUILD follows the `device` key (the reference strips the transform when it builds for a GPU, :238-244); a
             # stored "L2norm,Flat" file is FAISS's IndexPreTransform whatever it is loaded onto: None lets the loaders choose
             # FAISS's arithmetic for such a file
             l2norm_form = "faiss" if device is None else "numpy"
+        if load and file is None:
+            raise ValueError("load=True needs `file` (the path passed to save_faiss_index / save_path)")
+        index = make_flat_index(device=device, string_factory=string_factory, metric_type=metric_type, tie_order=tie_order,
+                                l2norm_form=l2norm_form)
         if load:
-            if file is None:
-                raise ValueError("load=True needs `file` (the path passed to save_faiss_index / save_path)")
-            index = make_flat_index(device=device, string_factory=string_factory, metric_type=metric_type, tie_order=tie_order,
-                                    l2norm_form=l2norm_form)
-            if isinstance(index, ShardedFlatIndex):
-                index.load_rows(file)  # every rank reads only its own row range
-            elif isinstance(index, MI355XFlatIndex):
-                index = MI355XFlatIndex.load(file, device=device, tie_order=tie_order, l2norm_form=l2norm_form)
-            else:
-                index.load_rows(file)  # LocalShardsFlatIndex: metric and "L2norm," from the file, set on EVERY shard
+            index.load_rows(file)  # metric and "L2norm," from the file; a sharded index reads each shard's row range only
         else:
-            index = make_flat_index(device=device, string_factory=string_factory, metric_type=metric_type, tie_order=tie_order,
-                                    l2norm_form=l2norm_form)
             index.add_vectors(self.dataset, column=column, batch_size=batch_size, train_size=train_size,
                               faiss_verbose=faiss_verbose)
             if save_path is not None:

@@ -22,14 +22,17 @@ one MI355XFlatIndex over the whole matrix returns.
 ``local_index`` / ``merge_fn`` are injection points used by the CPU (gloo) tests, which cannot run
 HIP kernels; the defaults are the HIP implementations and there is no CPU fallback.
 """
+import contextlib
+import itertools
 import os
-import struct
 from typing import Optional
 
 import numpy as np
 
-from .index import (BatchedSearchResults, BaseIndex, SearchResults, MI355XFlatIndex, METRIC_L2, MAX_K, FLAG_PHASE_FRONT,
-                    FLAG_PHASE_TAIL, _SCREEN_QUERY_CHUNK, index_file_format, index_file_header, parse_string_factory, query_chunks)
+from . import _lib
+from .index import (HostBoundaryIndex, MI355XFlatIndex, METRIC_L2, MERGE_TIE_ID_DESC, FLAG_PHASE_FRONT, FLAG_PHASE_TAIL,
+                    _SCREEN_QUERY_CHUNK, _resolve_device, check_search_args, index_file_format, index_file_header,
+                    iter_arrow_column, parse_string_factory, query_chunks, read_index_file_header, whole_panel_blocks)
 
 
 _FLT_MAX = float(np.finfo(np.float32).max)
@@ -75,14 +78,12 @@ def _gathered_views(buf, world, nq, k):
 
 def _merge_metric(metric, tie_order):
     """`metric` argument of the mq_topk_merge_* entries: the metric, OR-ed with MQ_MERGE_TIE_ID_DESC."""
-    from .index import MERGE_TIE_ID_DESC
     return int(metric) | (MERGE_TIE_ID_DESC if tie_order == "id_desc" else 0)
 
 
 def _hip_merge_records(records, world, nq, k, metric, tie_order="id_asc"):
     """All-gathered records (CUDA uint8 [world * record_bytes]) -> merged (D, I) through the C ABI."""
     import torch
-    from . import _lib
     lib = _lib.load()
     D = torch.empty((nq, k), dtype=torch.float32, device=records.device)
     I = torch.empty((nq, k), dtype=torch.int64, device=records.device)
@@ -96,7 +97,6 @@ def _hip_merge_records(records, world, nq, k, metric, tie_order="id_asc"):
 def _hip_merge(Ds, Is, metric, tie_order="id_asc"):
     """[W,nq,k] contiguous CUDA tensors -> merged (D, I) through mq_topk_merge_f32."""
     import torch
-    from . import _lib
     lib = _lib.load()
     W, nq, k = Ds.shape
     Ds, Is = Ds.contiguous(), Is.contiguous()
@@ -115,75 +115,11 @@ def _fill_empty(D, I, metric):
     I.fill_(-1)
 
 
-class _ShardedBase(BaseIndex):
-    """search / search_batch in terms of search_device (shared by both sharded classes)."""
-
-    def _query_device(self):
-        raise NotImplementedError
-
-    def __reduce__(self):  # see MI355XFlatIndex.__reduce__
-        raise TypeError(f"{type(self).__name__} lives in HBM and cannot be pickled: use save()")
-
-    def search_batch(self, queries, k: int = 10, **kwargs) -> BatchedSearchResults:
-        """The host boundary of MI355XFlatIndex.search_batch: page-locked staging buffers kept by the index, asynchronous copies
-        on the search stream, ONE synchronisation (not a pageable upload and two blocking downloads per batch)."""
-        import torch
-        from .index import _PINNED_IO_MAX_QUERIES
-        queries = np.asarray(queries)
-        if len(queries.shape) != 2:
-            raise ValueError("Shape of query must be 2D")
-        dev = self._query_device()
-        nq, d = queries.shape
-        on_gpu = torch.device(dev).type == "cuda"  # (the gloo CPU tests serve the local index from the oracle: plain copies there)
-        if not on_gpu or nq == 0 or nq > _PINNED_IO_MAX_QUERIES:
-            q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
-            D, I = self.search_device(q, k)
-            if on_gpu:
-                torch.cuda.current_stream(dev).synchronize()
-            return BatchedSearchResults(D.cpu().numpy(), I.cpu().numpy().astype(int))
-        io = getattr(self, "_io", None)
-        if io is None or io[0].shape[0] < nq or io[0].shape[1] != d or io[2].shape[1] != k or io[1].device != dev:
-            cap = max(256, 1 << (int(nq) - 1).bit_length())
-            io = self._io = (torch.empty((cap, d), dtype=torch.float32).pin_memory(), torch.empty((cap, d), dtype=torch.float32, device=dev),
-                             torch.empty((cap, k), dtype=torch.float32).pin_memory(), torch.empty((cap, k), dtype=torch.int64).pin_memory())
-        q_pin, q_dev, D_pin, I_pin = io
-        np.copyto(q_pin[:nq].numpy(), queries, casting="same_kind" if queries.dtype.kind == "f" else "unsafe")
-        with torch.cuda.device(dev):
-            q_dev[:nq].copy_(q_pin[:nq], non_blocking=True)
-            D, I = self.search_device(q_dev[:nq], k)
-            D_pin[:nq].copy_(D, non_blocking=True)
-            I_pin[:nq].copy_(I, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
-        return BatchedSearchResults(D_pin[:nq].numpy().copy(), I_pin[:nq].numpy().astype(int))
-
-    def _chunk_buffers(self, n, k, dev, slot):
-        """(record, gathered) of one <= 4096-query chunk, kept per (n, k) in two alternating slots: chunk i's buffers are still
-        being gathered / merged while chunk i + 1 scans into the other pair."""
-        import torch
-        cache = self.__dict__.setdefault("_chunk_cache", {})
-        key = (n, k, str(dev), slot)
-        buf = cache.get(key)
-        if buf is None:
-            if len(cache) > 16:
-                cache.clear()
-            rec_bytes, _ = record_layout(n, k)
-            record = torch.empty(rec_bytes, dtype=torch.uint8, device=dev)
-            gathered = torch.empty(self.world * rec_bytes, dtype=torch.uint8, device=dev) if (self.world > 1 or getattr(self, "always_gather", False)) else record
-            buf = cache[key] = (record, gathered)
-        return buf
-
-    def search(self, query, k: int = 10, **kwargs) -> SearchResults:
-        query = np.asarray(query)
-        if len(query.shape) != 1 and (len(query.shape) != 2 or query.shape[0] != 1):
-            raise ValueError("Shape of query is incorrect, it has to be either a 1D array or 2D (1, N)")
-        scores, indices = self.search_batch(query.reshape(1, -1), k)
-        return SearchResults(scores[0], indices[0].astype(int))
-
-
-class ShardedFlatIndex(_ShardedBase):
+class ShardedFlatIndex(HostBoundaryIndex):
     def __init__(self, string_factory: Optional[str] = None, metric_type: Optional[int] = None, group=None,
                  local_index=None, merge_fn=None, device=None, screen=None, always_gather=False, tie_order=None, l2norm_form=None):
         import torch.distributed as dist
+        super().__init__()
         self.group = group
         # always_gather: run the collective and the record merge even with ONE rank (tests / 1-GPU profiling of the N>1 path)
         self.always_gather = bool(always_gather) and dist.is_initialized()
@@ -192,9 +128,7 @@ class ShardedFlatIndex(_ShardedBase):
         self.metric_type = METRIC_L2 if metric_type is None else int(metric_type)
         self.string_factory = string_factory
         self.do_l2norm = parse_string_factory(string_factory)
-        self._l2norm_form = l2norm_form  # None: the index class's default on add, FAISS's form for a loaded "L2norm,Flat" file
         if local_index is None:
-            from .index import _resolve_device
             local_index = MI355XFlatIndex(device=device, string_factory=string_factory, metric_type=metric_type, screen=screen,
                                           tie_order=tie_order, l2norm_form=l2norm_form)
             # resolved NOW: a rank whose shard turns out empty still needs a device for its records
@@ -204,6 +138,7 @@ class ShardedFlatIndex(_ShardedBase):
         self.merge_fn = merge_fn  # None -> mq_topk_merge_records_f32 on the gathered buffer
         self.ntotal = 0
         self.d = getattr(local_index, "d", None)
+        self._chunk_cache = {}  # (n, k, device, slot) -> (record, gathered) of search_device's chunks
 
     # ---------------------------------------------------------------- construction
     def _set_total(self, n, d=None):
@@ -228,33 +163,39 @@ class ShardedFlatIndex(_ShardedBase):
         self._set_total(n_total, rows.shape[1])
 
     def add_vectors(self, vectors, column: Optional[str] = None, **kwargs):
-        if column is not None:
-            from .index import iter_arrow_column
-            n = len(vectors)
-            lo, hi = shard_bounds(n, self.world, self.rank)
-            self.local.id_offset = lo
-            pend = None
-            d = None
-            # only THIS rank's rows are decoded (host time and IO scale with N, not world x N)
-            for part in iter_arrow_column(vectors, column, lo, hi):
-                d = part.shape[1]
-                pend = part if pend is None else np.concatenate([pend, part])
-                full = (pend.shape[0] // 64) * 64
-                if full:
-                    self.local.add(pend[:full], total_hint=hi - lo)
-                    pend = pend[full:]
-            if d is None and n:  # an empty shard still needs the dimension
-                for first in iter_arrow_column(vectors, column, 0, 1):
-                    d = first.shape[1]
-            if pend is not None and pend.shape[0]:
-                self.local.add(pend, total_hint=hi - lo)
-            self._set_total(n, d)
-        else:
-            self.add_global(vectors)
+        if column is None:
+            return self.add_global(vectors)
+        n = len(vectors)
+        lo, hi = shard_bounds(n, self.world, self.rank)
+        self.local.id_offset = lo
+        d = None
+        # only THIS rank's rows are decoded (host time and IO scale with N, not world x N)
+        for block in whole_panel_blocks(iter_arrow_column(vectors, column, lo, hi)):
+            d = block.shape[1]
+            self.local.add(block, total_hint=hi - lo)
+        if d is None and n:  # an empty shard still needs the dimension
+            for first in iter_arrow_column(vectors, column, 0, 1):
+                d = first.shape[1]
+        self._set_total(n, d)
 
     # ---------------------------------------------------------------- search
     def _query_device(self):
         return getattr(self.local, "_torch_device", None) or "cpu"
+
+    def _chunk_buffers(self, n, k, dev, slot):
+        """(record, gathered) of one <= 4096-query chunk, kept per (n, k) in two alternating slots: chunk i's buffers are still
+        being gathered / merged while chunk i + 1 scans into the other pair."""
+        import torch
+        key = (n, k, str(dev), slot)
+        buf = self._chunk_cache.get(key)
+        if buf is None:
+            if len(self._chunk_cache) > 16:
+                self._chunk_cache.clear()
+            rec_bytes, _ = record_layout(n, k)
+            record = torch.empty(rec_bytes, dtype=torch.uint8, device=dev)
+            gathered = torch.empty(self.world * rec_bytes, dtype=torch.uint8, device=dev) if (self.world > 1 or self.always_gather) else record
+            buf = self._chunk_cache[key] = (record, gathered)
+        return buf
 
     def _scan(self, q, k, record):
         """Local shard scan of one chunk, results written into the record's D / I views."""
@@ -284,10 +225,7 @@ class ShardedFlatIndex(_ShardedBase):
         chunk's collective and merge are exposed."""
         import torch
         import torch.distributed as dist
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        if k > MAX_K:
-            raise NotImplementedError(f"k={k} > {MAX_K}")
+        check_search_args(queries, k, self.d)
         nq = queries.shape[0]
         dev = queries.device
         if (self.world == 1 and not self.always_gather and isinstance(self.local, MI355XFlatIndex) and self.local.ntotal > 0
@@ -297,6 +235,10 @@ class ShardedFlatIndex(_ShardedBase):
         D = torch.empty((nq, k), dtype=torch.float32, device=dev)
         I = torch.empty((nq, k), dtype=torch.int64, device=dev)
         pending = None  # (work, gathered, s, n)
+
+        def gather(record, gathered):  # -> the collective's handle; one rank's record IS the gathered buffer (_chunk_buffers)
+            if self.world > 1 or self.always_gather:
+                return dist.all_gather_into_tensor(gathered, record, group=self.group, async_op=True)
 
         def finish(p):
             work, gathered, s, n = p
@@ -333,10 +275,7 @@ class ShardedFlatIndex(_ShardedBase):
                 tail.wait_event(scanned)
                 with torch.cuda.stream(tail):
                     self.local.search_phase(q, k, out, ws, FLAG_PHASE_TAIL, tail)
-                    if self.world > 1 or self.always_gather:
-                        work = dist.all_gather_into_tensor(gathered, record, group=self.group, async_op=True)
-                    else:
-                        work = None
+                    work = gather(record, gathered)
                     if pending is not None:
                         finish(pending)
                         ev = torch.cuda.Event()
@@ -353,10 +292,7 @@ class ShardedFlatIndex(_ShardedBase):
             # the chunk two back has been merged (finish() below runs before the next scan is enqueued on the same stream)
             record, gathered = self._chunk_buffers(n, k, dev, ci & 1)
             self._scan(q, k, record)
-            if self.world > 1 or self.always_gather:
-                work = dist.all_gather_into_tensor(gathered, record, group=self.group, async_op=True)
-            else:
-                work = None
+            work = gather(record, gathered)
             if pending is not None:
                 finish(pending)
             pending = (work, gathered, s, n)
@@ -389,37 +325,32 @@ class ShardedFlatIndex(_ShardedBase):
 
     def load_rows(self, file):
         """Fill this (empty) sharded index from a whole-matrix file: every rank reads only its row range."""
-        from .index import read_index_file_header
         path = os.fspath(file)
         n, d, metric, l2norm, data_off = read_index_file_header(path)
-        lo, hi = shard_bounds(n, self.world, self.rank)
-        self.local.id_offset = lo
-        # FaissIndex.load reads metric and transform from the FILE (datasets/search.py:399-416): a load config may omit
-        # string_factory / metric_type, so the shard must scan with what the file says, like _merge and _fill_empty do
         if getattr(self.local, "ntotal", 0):
             raise ValueError("load_rows fills an EMPTY sharded index")
+        lo, hi = shard_bounds(n, self.world, self.rank)
+        self.local.id_offset = lo
+        # metric and transform come from the FILE, for the shard's scan like for _merge and _fill_empty (an injected local
+        # index, the CPU tests' oracle stand-in, takes neither: it stores and scans rows as they are given)
         self.metric_type, self.do_l2norm = int(metric), bool(l2norm)
         self.string_factory = "L2norm,Flat" if l2norm else "Flat"
-        self.local.metric_type = int(metric)
-        if hi > lo:
-            rows = np.fromfile(path, dtype=np.float32, count=(hi - lo) * d, offset=data_off + lo * d * 4).reshape(hi - lo, d)
-            self.local.do_l2norm = False  # stored rows are already normalised
-            self.local.add(rows, total_hint=hi - lo)
-        self.local.do_l2norm = bool(l2norm)
-        if l2norm and hasattr(self.local, "l2norm_form"):  # like MI355XFlatIndex.load: a stored "L2norm,Flat" index is FAISS's object
-            self.local.l2norm_form = self._l2norm_form or os.environ.get("MQ_KNN_L2NORM_FORM", "faiss")
+        with self.local._stored_rows(metric, l2norm) if isinstance(self.local, MI355XFlatIndex) else contextlib.nullcontext():
+            if hi > lo:
+                self.local.add(np.fromfile(path, dtype=np.float32, count=(hi - lo) * d, offset=data_off + lo * d * 4).reshape(hi - lo, d),
+                               total_hint=hi - lo)
         self._set_total(n, d)
         return self
 
 
-class LocalShardsFlatIndex(_ShardedBase):
+class LocalShardsFlatIndex(HostBoundaryIndex):
     """One process, several GPUs (``device=-1`` or ``device=[...]``): a MI355XFlatIndex per device, records
     copied peer-to-peer to the first device, merged there."""
 
     def __init__(self, devices, string_factory: Optional[str] = None, metric_type: Optional[int] = None, screen=None,
                  allow_repeated_devices=False, tie_order=None, l2norm_form=None):
         import torch
-        from . import _lib
+        super().__init__()
         _lib.require_gpu()
         devices = [int(x) for x in devices]
         # allow_repeated_devices: several shards on one GPU (exercises the N-shard path on a 1-GPU box)
@@ -432,7 +363,6 @@ class LocalShardsFlatIndex(_ShardedBase):
         self.metric_type = METRIC_L2 if metric_type is None else int(metric_type)
         self.string_factory = string_factory
         self.do_l2norm = parse_string_factory(string_factory)
-        self._l2norm_form = l2norm_form
         self.shards = [MI355XFlatIndex(device=g, string_factory=string_factory, metric_type=metric_type, screen=screen,
                                        tie_order=tie_order, l2norm_form=l2norm_form) for g in devices]
         self.tie_order = self.shards[0].tie_order
@@ -446,66 +376,53 @@ class LocalShardsFlatIndex(_ShardedBase):
 
     def add_vectors(self, vectors, column: Optional[str] = None, **kwargs):
         if column is not None:
-            from .index import iter_arrow_column
             blocks = iter_arrow_column(vectors, column)
         else:
             mat = np.asarray(vectors, dtype=np.float32)
             if mat.ndim != 2:
                 raise ValueError("expected a 2-D matrix of vectors")
-            blocks = iter([mat])
+            blocks = [mat]
         n = len(vectors)
         bounds = [shard_bounds(n, self.world, r) for r in range(self.world)]
         for sh, (lo, _) in zip(self.shards, bounds):
             sh.id_offset = lo
-        seen = 0
-        pend = [None] * self.world
-        for block in blocks:
-            self.d = block.shape[1]
-            b_lo, b_hi = seen, seen + block.shape[0]
-            seen = b_hi
-            for r, (lo, hi) in enumerate(bounds):
-                s, e = max(lo, b_lo), min(hi, b_hi)
-                if s >= e:
-                    continue
-                part = block[s - b_lo:e - b_lo]
-                pend[r] = part if pend[r] is None else np.concatenate([pend[r], part])
-                full = (pend[r].shape[0] // 64) * 64
-                if full:
-                    self.shards[r].add(pend[r][:full], total_hint=hi - lo)
-                    pend[r] = pend[r][full:]
-        for r, (lo, hi) in enumerate(bounds):
-            if pend[r] is not None and pend[r].shape[0]:
-                self.shards[r].add(pend[r], total_hint=hi - lo)
+
+        def routed():  # (shard, its rows of the block): the blocks come in row order, so shard after shard
+            seen = 0
+            for block in blocks:
+                self.d = block.shape[1]
+                for r, (lo, hi) in enumerate(bounds):
+                    s, e = max(lo, seen), min(hi, seen + block.shape[0])
+                    if s < e:
+                        yield r, block[s - seen:e - seen]
+                seen += block.shape[0]
+
+        for r, parts in itertools.groupby(routed(), key=lambda rp: rp[0]):
+            for block in whole_panel_blocks(part for _, part in parts):
+                self.shards[r].add(block, total_hint=bounds[r][1] - bounds[r][0])
         self.ntotal = n
 
     def load_rows(self, file):
         """Fill this (empty) index from a whole-matrix file (own format or a FAISS Flat file): metric and the "L2norm,"
         transform come from the file, like FaissIndex.load; the stored rows are already normalised, the QUERIES of every
         shard are normalised at search time."""
-        from .index import read_index_file_header
         path = os.fspath(file)
         n, d, metric, l2norm, data_off = read_index_file_header(path)
         if self.ntotal:
             raise ValueError("load_rows fills an EMPTY index")
         self.metric_type, self.do_l2norm = int(metric), bool(l2norm)
         self.string_factory = "L2norm,Flat" if l2norm else "Flat"
-        for sh in self.shards:
-            sh.metric_type, sh.do_l2norm = int(metric), False
-        if n:
-            self.add_vectors(np.memmap(path, dtype=np.float32, mode="r", offset=data_off, shape=(n, d)))
-        for sh in self.shards:
-            sh.do_l2norm = bool(l2norm)
-            if l2norm:  # like MI355XFlatIndex.load: a stored "L2norm,Flat" index is FAISS's object
-                sh.l2norm_form = self._l2norm_form or os.environ.get("MQ_KNN_L2NORM_FORM", "faiss")
+        with contextlib.ExitStack() as stack:
+            for sh in self.shards:
+                stack.enter_context(sh._stored_rows(metric, l2norm))
+            if n:
+                self.add_vectors(np.memmap(path, dtype=np.float32, mode="r", offset=data_off, shape=(n, d)))
         self.ntotal, self.d = n, (d or None)
         return self
 
     def search_device(self, queries, k):
         import torch
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        if k > MAX_K:
-            raise NotImplementedError(f"k={k} > {MAX_K}")
+        check_search_args(queries, k, self.d)
         nq = queries.shape[0]
         dev0 = self.shards[0]._torch_device
         rec_bytes, _ = record_layout(nq, k)
