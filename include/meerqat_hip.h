@@ -789,6 +789,26 @@ int mq_bm25_search_f32(const int64_t *ptr_dev, const int32_t *doc_dev, const flo
                        const int32_t *qptr_dev, const int32_t *cterm_dev, const float *cweight_dev, int nq, int k, int flags,
                        int64_t id_offset, float *D_dev, int64_t *I_dev, void *ws_dev, size_t ws_bytes, size_t budget_bytes,
                        void *stream);
+/* Parameter grid (the reference's `hp bm25` job): G settings of (k1, b), each given as its norm cache (caches [G][256] fp32, device),
+ * searched over the SAME index without touching its impact array.  One sweep of the postings scores a tile of settings: a posting's
+ * impact under setting g is float(tf / (tf + caches[g][code[doc]])) (the division in double), then weight * impact and the sum as in
+ * mq_bm25_search_f32 -- D / I [G, nq, k] hold, slice by slice, bit for bit what mq_bm25_impacts_f32 with caches[g] followed by
+ * mq_bm25_search_f32 gives.
+ * mq_bm25_grid_tile: the most settings one sweep scores.  mq_bm25_grid_block_rows(g): documents per scoring workgroup when a tile
+ *   holds g settings -- MQ_BM25_BLOCK_ROWS over the next power of two >= g (g = 1: mq_bm25_block_rows()); 0 outside 1 ... tile.
+ * mq_bm25_grid_chunk_queries(N, nq, g, budget_bytes): queries per launch for a tile of g settings -- the most that keep the dense
+ *   [g, chunk, N] fp32 score matrix within budget_bytes, g * chunk within the 65535 rows of a selection launch and the scoring launch
+ *   below 2^31 threads; at least one.  ws: mq_bm25_grid_workspace_bytes(N, nq, min(G, tile), k, budget_bytes).
+ * mq_bm25_search_grid_f32 walks the G settings in tiles (a last one may be partial) and the queries in chunks; results depend on
+ *   neither.  Validation (before any HIP call) and the NULL conventions are mq_bm25_search_f32's; G < 1 is MQ_EINVAL. */
+int mq_bm25_grid_tile(void);
+int mq_bm25_grid_block_rows(int g);
+int mq_bm25_grid_chunk_queries(int64_t N, int nq, int g, size_t budget_bytes);
+size_t mq_bm25_grid_workspace_bytes(int64_t N, int nq, int g, int k, size_t budget_bytes);
+int mq_bm25_search_grid_f32(const int64_t *ptr_dev, const int32_t *doc_dev, const int32_t *tf_dev, const uint8_t *code_dev,
+                            const float *caches_dev, int G, int64_t N, int64_t n_terms, const int32_t *qptr_dev,
+                            const int32_t *cterm_dev, const float *cweight_dev, int nq, int k, int flags, int64_t id_offset,
+                            float *D_dev, int64_t *I_dev, void *ws_dev, size_t ws_bytes, size_t budget_bytes, void *stream);
 
 /* ---- face detection: MTCNN (csrc/mtcnn.hip) -- what the reference runs through facenet_pytorch on a CUDA machine
  * (meerqat/image/face_detection.py).  The arithmetic restates the published detect_face (tests/mtcnn_restatement.py lists every

@@ -122,6 +122,12 @@ SIGNATURES = {
     "mq_bm25_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_sz]),
     "mq_bm25_search_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_i64, c_ptr, c_ptr,
                                    c_ptr, c_sz, c_sz, c_ptr]),
+    "mq_bm25_grid_tile": (c_int, []),
+    "mq_bm25_grid_block_rows": (c_int, [c_int]),
+    "mq_bm25_grid_chunk_queries": (c_int, [c_i64, c_int, c_int, c_sz]),
+    "mq_bm25_grid_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_int, c_sz]),
+    "mq_bm25_search_grid_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int,
+                                        c_i64, c_ptr, c_ptr, c_ptr, c_sz, c_sz, c_ptr]),
     "mq_mtcnn_weight_floats": (c_int, [c_int]),
     "mq_mtcnn_resample_u8_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr]),
     "mq_mtcnn_pnet_f32": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_ptr, ctypes.c_float, c_int, c_int, c_ptr, c_ptr, c_ptr,

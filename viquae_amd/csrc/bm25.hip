@@ -100,6 +100,109 @@ __global__ __launch_bounds__(ST) void bm25_score_kernel(const int64_t* __restric
     for (int i = tid; i < rows; i += ST) out[i] = acc[i];
 }
 
+// Parameter grid: GT settings of (k1, b) scored in ONE sweep of the postings.  What a setting changes is the 256-entry norm cache
+// alone, so a workgroup keeps GT accumulators per document (RG = R / GT documents: the same 64 KiB) and the tile's caches in LDS,
+// both with the setting as the fast index -- a lane's posting then reads and writes GT consecutive floats (128-bit LDS accesses).
+// Per posting and setting the arithmetic is bm25_impact_kernel's followed by bm25_score_kernel's, in that order: the double
+// division, its rounding to float, the float product with the clause weight, the float sum in clause order.  `gt` <= GT settings
+// are live (a last, partial tile); the others compute on a zero cache and are not stored.  scores: [gt, n, N], n = gridDim.y.
+template <int GT>
+struct GridShape {
+    static constexpr int RG = R / GT;
+    static constexpr bool STAGE_CODES = GT >= 2;  // the block's length codes in LDS (at GT = 1 they would cost a workgroup per CU)
+    static constexpr int CODE_BYTES = STAGE_CODES ? RG : 16;
+};
+
+template <int GT>
+__device__ __forceinline__ void load_row(float (&v)[GT], const float* __restrict__ p) {
+    if constexpr (GT % 4 == 0) {
+#pragma unroll
+        for (int j = 0; j < GT / 4; ++j) {
+            const float4 x = reinterpret_cast<const float4*>(p)[j];
+            v[4 * j] = x.x; v[4 * j + 1] = x.y; v[4 * j + 2] = x.z; v[4 * j + 3] = x.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < GT; ++j) v[j] = p[j];
+    }
+}
+
+template <int GT>
+__device__ __forceinline__ void store_row(float* __restrict__ p, const float (&v)[GT]) {
+    if constexpr (GT % 4 == 0) {
+#pragma unroll
+        for (int j = 0; j < GT / 4; ++j) reinterpret_cast<float4*>(p)[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < GT; ++j) p[j] = v[j];
+    }
+}
+
+template <int GT>
+__global__ __launch_bounds__(ST) void bm25_score_grid_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ doc,
+                                                             const int32_t* __restrict__ tf, const uint8_t* __restrict__ code,
+                                                             const float* __restrict__ caches, int gt, int64_t N, int64_t n_terms,
+                                                             const int32_t* __restrict__ qptr, const int32_t* __restrict__ cterm,
+                                                             const float* __restrict__ cweight, float* __restrict__ scores) {
+    constexpr int RG = GridShape<GT>::RG;
+    __shared__ __attribute__((aligned(16))) float acc[RG * GT];     // [document][setting]
+    __shared__ __attribute__((aligned(16))) float norm[256 * GT];   // [length code][setting]
+    __shared__ uint8_t lcode[GridShape<GT>::CODE_BYTES];
+    __shared__ int64_t bound[2 * CB];
+    const int tid = threadIdx.x;
+    const int q = blockIdx.y;
+    const int64_t base = (int64_t)blockIdx.x * RG;
+    const int rows = (int)min((int64_t)RG, N - base);
+    for (int i = tid; i < RG * GT; i += ST) acc[i] = 0.f;
+    for (int i = tid; i < 256 * GT; i += ST) {
+        const int c = i / GT, g = i % GT;
+        norm[i] = g < gt ? caches[g * 256 + c] : 0.f;
+    }
+    if constexpr (GridShape<GT>::STAGE_CODES)
+        for (int i = tid; i < RG; i += ST) lcode[i] = i < rows ? code[base + i] : (uint8_t)0;
+    const int cbeg = qptr[q], cend = qptr[q + 1];
+    for (int c0 = cbeg; c0 < cend; c0 += CB) {
+        const int nc = min(CB, cend - c0);
+        __syncthreads();  // LDS is initialised / the previous batch's bounds are no longer read
+        if (tid < 2 * nc) {
+            const int t = cterm[c0 + (tid >> 1)];
+            bound[tid] = (t < 0 || t >= n_terms) ? 0 : lower_bound(doc, ptr[t], ptr[t + 1], base + (int64_t)(tid & 1) * RG);
+        }
+        __syncthreads();
+        for (int c = 0; c < nc; ++c) {
+            const int64_t lo = bound[2 * c], hi = bound[2 * c + 1];
+            if (lo == hi) continue;  // uniform over the workgroup
+            const float w = cweight[c0 + c];
+            for (int64_t p = lo + tid; p < hi; p += ST) {
+                const int d = (int)((int64_t)doc[p] - base);
+                if ((unsigned)d >= (unsigned)rows) continue;  // (never, for sorted postings of documents below N)
+                const double f = (double)tf[p];
+                int lc;
+                if constexpr (GridShape<GT>::STAGE_CODES) lc = lcode[d]; else lc = code[base + d];
+                float a[GT], nv[GT];
+                load_row<GT>(a, acc + d * GT);
+                load_row<GT>(nv, norm + lc * GT);
+#pragma unroll
+                for (int g = 0; g < GT; ++g) {
+                    const float impact = (float)(f / (f + (double)nv[g]));
+                    a[g] = __fadd_rn(a[g], __fmul_rn(w, impact));
+                }
+                store_row<GT>(acc + d * GT, a);
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    const int64_t n = gridDim.y;
+    for (int i = tid; i < rows; i += ST) {
+        float a[GT];
+        load_row<GT>(a, acc + i * GT);
+#pragma unroll
+        for (int g = 0; g < GT; ++g)
+            if (g < gt) scores[((int64_t)g * n + q) * N + base + i] = a[g];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- top-k
 struct Select {
     uint64_t prefix;  // the decided high bits of the k-th key, the undecided ones zero
@@ -289,6 +392,28 @@ int topk_rows(const float* scores, int rows, int64_t N, int k, int flags, int64_
 
 constexpr int MAX_ROWS_PER_CALL = 65535;  // gridDim.y
 
+constexpr int GRID_TILE = 8;  // settings per sweep: 2,048 documents x 8 accumulators, 78 KiB of LDS, two workgroups per CU
+
+// the instantiated tile width that holds g settings: the next power of two
+inline int grid_width(int g) {
+    int w = 1;
+    while (w < g) w <<= 1;
+    return w;
+}
+
+struct GridArgs {
+    const int64_t* ptr; const int32_t* doc; const int32_t* tf; const uint8_t* code;
+    int64_t N, n_terms;
+    const int32_t* qptr; const int32_t* cterm; const float* cweight;
+};
+
+template <int GT>
+void launch_grid(const GridArgs& a, const float* caches, int gt, int q0, int n, float* scores, hipStream_t st) {
+    const unsigned blocks = (unsigned)((a.N + GridShape<GT>::RG - 1) / GridShape<GT>::RG);
+    hipLaunchKernelGGL(bm25_score_grid_kernel<GT>, dim3(blocks, n), dim3(ST), 0, st, a.ptr, a.doc, a.tf, a.code, caches, gt, a.N,
+                       a.n_terms, a.qptr + q0, a.cterm, a.cweight, scores);
+}
+
 }  // namespace
 
 extern "C" {
@@ -362,6 +487,86 @@ int mq_bm25_search_f32(const int64_t* ptr_dev, const int32_t* doc_dev, const flo
         BM25_HIP(hipGetLastError());
         const int rc = topk_rows(scores, n, N, k, flags, id_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k, sel, st);
         if (rc != MQ_OK) return rc;
+    }
+    return MQ_OK;
+}
+
+int mq_bm25_grid_tile(void) { return GRID_TILE; }
+
+int mq_bm25_grid_block_rows(int g) {
+    if (g < 1 || g > GRID_TILE) return 0;
+    return R / grid_width(g);
+}
+
+int mq_bm25_grid_chunk_queries(int64_t N, int nq, int g, size_t budget_bytes) {
+    if (N < 1 || nq < 1 || g < 1 || g > GRID_TILE) return 0;
+    int64_t c = (int64_t)(budget_bytes / ((size_t)g * (size_t)N * sizeof(float)));
+    if (c > nq) c = nq;
+    if (c > MAX_ROWS_PER_CALL / g) c = MAX_ROWS_PER_CALL / g;  // one selection launch takes the tile's g * c rows
+    const int64_t rg = R / grid_width(g);
+    const int64_t grid_cap = ((int64_t)1 << 31) / ST / ((N + rg - 1) / rg);  // threads of one scoring launch stay below 2^31
+    if (c > grid_cap) c = grid_cap;
+    if (c < 1) c = 1;
+    return (int)c;
+}
+
+size_t mq_bm25_grid_workspace_bytes(int64_t N, int nq, int g, int k, size_t budget_bytes) {
+    const int c = mq_bm25_grid_chunk_queries(N, nq, g, budget_bytes);
+    if (c < 1 || k < 1 || k > MQ_KNN_MAX_K) return 0;
+    // the score matrix, the selection's scratch, and the tile's [g * c, k] results before they go to their slices of D / I
+    return align256((size_t)g * (size_t)c * (size_t)N * sizeof(float)) + topk_layout(g * c, k).total +
+           align256((size_t)g * c * k * sizeof(float)) + align256((size_t)g * c * k * sizeof(int64_t));
+}
+
+int mq_bm25_search_grid_f32(const int64_t* ptr_dev, const int32_t* doc_dev, const int32_t* tf_dev, const uint8_t* code_dev,
+                            const float* caches_dev, int G, int64_t N, int64_t n_terms, const int32_t* qptr_dev,
+                            const int32_t* cterm_dev, const float* cweight_dev, int nq, int k, int flags, int64_t id_offset,
+                            float* D_dev, int64_t* I_dev, void* ws_dev, size_t ws_bytes, size_t budget_bytes, void* stream) {
+    // doc / tf / cterm / cweight may be NULL only when there is nothing behind them, as for mq_bm25_search_f32
+    if (!ptr_dev || !code_dev || !caches_dev || !qptr_dev || !D_dev || !I_dev || !ws_dev || G < 1 || N < 1 || N > 0x7fffffffLL ||
+        n_terms < 0 || nq < 1 || k < 1)
+        return MQ_EINVAL;
+    if (flags & ~MQ_KNN_FLAG_TIE_ID_DESC) return MQ_EINVAL;
+    if (k > MQ_KNN_MAX_K) return MQ_EUNSUPPORTED;
+    const int tile = G < GRID_TILE ? G : GRID_TILE;
+    const int chunk = mq_bm25_grid_chunk_queries(N, nq, tile, budget_bytes);
+    if (ws_bytes < mq_bm25_grid_workspace_bytes(N, nq, tile, k, budget_bytes)) return MQ_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float* scores = static_cast<float*>(ws_dev);
+    char* sel = static_cast<char*>(ws_dev) + align256((size_t)tile * (size_t)chunk * (size_t)N * sizeof(float));
+    float* stage_D = reinterpret_cast<float*>(sel + topk_layout(tile * chunk, k).total);
+    int64_t* stage_I = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(stage_D) + align256((size_t)tile * chunk * k * sizeof(float)));
+    GridArgs a;
+    a.ptr = ptr_dev; a.doc = doc_dev; a.tf = tf_dev; a.code = code_dev; a.N = N; a.n_terms = n_terms;
+    a.qptr = qptr_dev; a.cterm = cterm_dev; a.cweight = cweight_dev;
+    for (int g0 = 0; g0 < G; g0 += GRID_TILE) {
+        const int gt = G - g0 < GRID_TILE ? G - g0 : GRID_TILE;
+        const float* caches = caches_dev + (size_t)g0 * 256;
+        for (int q0 = 0; q0 < nq; q0 += chunk) {
+            const int n = nq - q0 < chunk ? nq - q0 : chunk;
+            switch (grid_width(gt)) {
+                case 1: launch_grid<1>(a, caches, gt, q0, n, scores, st); break;
+                case 2: launch_grid<2>(a, caches, gt, q0, n, scores, st); break;
+                case 4: launch_grid<4>(a, caches, gt, q0, n, scores, st); break;
+                default: launch_grid<8>(a, caches, gt, q0, n, scores, st); break;
+            }
+            BM25_HIP(hipGetLastError());
+            if (n == nq) {  // the tile's rows (setting, query) are consecutive rows of D / I: one selection over all of them
+                const int rc = topk_rows(scores, gt * n, N, k, flags, id_offset, D_dev + (int64_t)g0 * nq * k,
+                                         I_dev + (int64_t)g0 * nq * k, sel, st);
+                if (rc != MQ_OK) return rc;
+                continue;
+            }
+            // a query chunk: the tile's rows are selected at once into the staging tables, then each setting's n rows are copied
+            // into its own slice of D / I (one strided copy per table)
+            const int rc = topk_rows(scores, gt * n, N, k, flags, id_offset, stage_D, stage_I, sel, st);
+            if (rc != MQ_OK) return rc;
+            const int64_t at = ((int64_t)g0 * nq + q0) * k;
+            BM25_HIP(hipMemcpy2DAsync(D_dev + at, (size_t)nq * k * sizeof(float), stage_D, (size_t)n * k * sizeof(float),
+                                      (size_t)n * k * sizeof(float), gt, hipMemcpyDeviceToDevice, st));
+            BM25_HIP(hipMemcpy2DAsync(I_dev + at, (size_t)nq * k * sizeof(int64_t), stage_I, (size_t)n * k * sizeof(int64_t),
+                                      (size_t)n * k * sizeof(int64_t), gt, hipMemcpyDeviceToDevice, st));
+        }
     }
     return MQ_OK;
 }

@@ -53,6 +53,7 @@ from ..index import (FLAG_TIE_ID_DESC, MAX_K, TIE_ORDERS, BaseIndex, BatchedSear
 MAX_TOKEN_LENGTH = 255
 DEFAULT_K1, DEFAULT_B = 1.2, 0.75            # Elasticsearch's defaults
 DEFAULT_WORKSPACE_BYTES = 1 << 30            # budget of the dense [query chunk, N] fp32 score matrix
+GRID_METHOD = "grid"                         # how search_grid scores a list of settings by default: "grid" | "loop" ("BM25": measured)
 _MAGIC = b"MQBM2501"
 _BUILD_DOCS = 1 << 16                        # documents whose (term, document) pairs are counted at once
 
@@ -381,6 +382,86 @@ class MI355XBM25Index(BaseIndex):
                                               self._ws.data_ptr(), self._ws.numel(), self.workspace_bytes, stream.cuda_stream),
                        "mq_bm25_search_f32")
         return D, I
+
+    # ------------------------------------------------------------------ parameter grid
+    def search_grid(self, queries, params, k: int = 10, method: Optional[str] = None):
+        """The queries under every ``(k1, b)`` of ``params`` at once: ``(D float32 [G, nq, k], I int64 [G, nq, k])`` as numpy arrays,
+        best first, unfilled slots ``(-inf, -1)``; slice g is, bit for bit, what ``set_bm25(*params[g])`` followed by
+        ``search_batch(queries, k)`` returns.  The index's own ``k1`` / ``b`` and its resident impacts are what they were afterwards.
+        ``method``: "grid" -- one sweep of the postings per tile of settings (``search_grid_device``) -- or "loop" -- per setting,
+        ``set_bm25`` + ``search_device``, the parameters restored at the end; None takes ``GRID_METHOD``.  Settings follow Lucene's
+        own rule: ``k1`` finite and >= 0, ``0 <= b <= 1``."""
+        import torch
+        method = method or GRID_METHOD
+        if method not in ("grid", "loop"):
+            raise ValueError(f"method must be 'grid' or 'loop', got {method!r}")
+        params = [(float(k1), float(b)) for k1, b in params]
+        if not params:
+            raise ValueError("params is empty: give at least one (k1, b)")
+        for k1, b in params:
+            if not (np.isfinite(k1) and k1 >= 0):
+                raise ValueError(f"illegal k1 value: {k1}, must be a non-negative finite value")
+            if not 0 <= b <= 1:  # (NaN fails both comparisons)
+                raise ValueError(f"illegal b value: {b}, must be between 0 and 1")
+        if isinstance(queries, (str, bytes)) or not hasattr(queries, "__len__"):
+            raise ValueError("queries must be a list of strings (or of term-id sequences)")
+        if self.ptr is None or self.ntotal == 0:
+            raise ValueError("the index is empty: call add_documents first")
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        if k > MAX_K:
+            raise NotImplementedError(f"k={k} > {MAX_K} (MQ_KNN_MAX_K)")
+        G, nq = len(params), len(queries)
+        if nq == 0:
+            return np.zeros((G, 0, k), np.float32), np.zeros((G, 0, k), np.int64)
+        qptr, cterm, cweight = self.pack_clauses(queries)
+        dev = self._torch_device
+        qptr, cterm, cweight = (torch.from_numpy(a).to(dev) for a in (qptr, cterm, cweight))
+        if method == "grid":
+            caches = torch.from_numpy(np.stack([norm_cache(k1, b, self.avgdl) for k1, b in params])).to(dev)
+            D, I = self.search_grid_device(qptr, cterm, cweight, caches, k)
+        else:
+            D = torch.empty((G, nq, k), dtype=torch.float32, device=dev)
+            I = torch.empty((G, nq, k), dtype=torch.int64, device=dev)
+            own = (self.k1, self.b)
+            try:
+                for g, (k1, b) in enumerate(params):
+                    self.set_bm25(k1, b)
+                    D[g], I[g] = self.search_device(qptr, cterm, cweight, k)
+            finally:
+                self.set_bm25(*own)
+        torch.cuda.current_stream(dev).synchronize()
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_grid_device(self, qptr, cterm, cweight, caches, k):
+        """The raw grid entry: clause arrays and the settings' norm caches (fp32 [G, 256], ``norm_cache`` rows) on the device ->
+        (D [G, nq, k] fp32, I [G, nq, k] int64) device tensors, enqueued on the current stream and not synchronised.  Reads the
+        postings' term frequencies and the length codes; the resident impacts are neither read nor written."""
+        import torch
+        lib, dev, d = _lib.load(), self._torch_device, self._dev
+        if caches.dim() != 2 or caches.shape[1] != 256 or caches.shape[0] < 1 or caches.dtype != torch.float32 or not caches.is_contiguous():
+            raise ValueError("caches must be a contiguous float32 [G, 256] tensor, G >= 1")
+        G, nq = caches.shape[0], qptr.numel() - 1
+        D = torch.empty((G, nq, k), dtype=torch.float32, device=dev)
+        I = torch.empty((G, nq, k), dtype=torch.int64, device=dev)
+        tile = min(G, int(lib.mq_bm25_grid_tile()))
+        nbytes = int(lib.mq_bm25_grid_workspace_bytes(self.ntotal, nq, tile, k, self.workspace_bytes))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        flags = FLAG_TIE_ID_DESC if self.tie_order == "id_desc" else 0
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _lib.check(lib.mq_bm25_search_grid_f32(d["ptr"].data_ptr(), d["doc"].data_ptr() or None, d["tf"].data_ptr() or None,
+                                                   d["codes"].data_ptr(), caches.data_ptr(), G, self.ntotal, self.vocabulary_size,
+                                                   qptr.data_ptr(), cterm.data_ptr() or None, cweight.data_ptr() or None, nq, k, flags, 0,
+                                                   D.data_ptr(), I.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                   self.workspace_bytes, stream.cuda_stream), "mq_bm25_search_grid_f32")
+        return D, I
+
+    def grid_query_chunk(self, nq, g):
+        """Queries scored per launch for a tile of ``g`` settings under this index's workspace budget."""
+        return int(_lib.load().mq_bm25_grid_chunk_queries(self.ntotal, int(nq), int(g), self.workspace_bytes))
 
     def query_chunk(self, nq):
         """Queries scored per launch under this index's workspace budget."""

@@ -32,7 +32,7 @@ import numpy as np
 
 from ..index import L2_DIRECT_BELOW
 from .runs import ArrayRun, dump_run
-from .search import KnowledgeBase
+from .search import IndexKind, KnowledgeBase
 
 
 _PUNCTUATION = str.maketrans("", "", string.punctuation)
@@ -297,7 +297,7 @@ class Searcher:
                 run.add_block(q_ids, block[0], block[1])
                 continue
             for q_id, sc, idx in zip(q_ids, scores.tolist(), indices.tolist()):
-                self._fill_run(kb, run.setdefault(q_id, {}), sc, idx)
+                self._fill_run(kb, run.setdefault(q_id, {}), *self._hits(kb, index_name, sc, idx))
         for index_name in list(waiting):
             file_waiting(index_name)
 
@@ -312,6 +312,15 @@ class Searcher:
         if csr is None:  # (dict.setdefault would build the CSR arrays again for EVERY query: its argument is evaluated first)
             csr = self._csr[id(kb)] = _Mapping(kb.index_mapping)
         return csr
+
+    @staticmethod
+    def _hits(kb, index_name, scores, indices):
+        """One query's (scores, indices) lists without the unfilled slots of a BM25 index -- ``(-inf, -1)`` behind the last passage
+        that shares a term with the question: a server returns only its hits, and -1 is no passage to judge."""
+        if kb.indexes[index_name].kind == IndexKind.BM25 and indices and indices[-1] < 0:
+            n = next(i for i, doc in enumerate(indices) if doc < 0)
+            return scores[:n], indices[:n]
+        return scores, indices
 
     def _fill_run(self, kb, run_q, scores, indices):
         """One query's hits -> run dict, cut at k entries (reference: search.py:413-440)."""
@@ -380,23 +389,27 @@ class Searcher:
                                                                                      question_types)):
                     if block is None:
                         run_q = run.setdefault(q_id, {})
-                        scores = np.asarray(scores).tolist()
-                        indices = np.asarray(indices).tolist()
+                        scores, indices = self._hits(kb, index_name, np.asarray(scores).tolist(), np.asarray(indices).tolist())
                         self._fill_run(kb, run_q, scores, indices)
                         run_keys = run_q.keys()
                     else:
                         ids_row = block[0][row]
                         run_keys = {str(i) for i in ids_row[ids_row >= 0].tolist()}
                     if self.reference_kb is not None:
-                        self.qrels.setdefault(q_id, {})
-                        self.qnonrels.setdefault(q_id, {})
-                        retrieved = run_keys - (self.qrels[q_id].keys() | self.qnonrels[q_id].keys())
-                        _, relevant = find_relevant(retrieved, gt["original_answer"], gt["answer"], self.reference_kb,
-                                                    reference_key=self.reference_key, question_type=question_type,
-                                                    passages=self._passage_texts())
-                        self.qrels[q_id].update({str(i): 1 for i in relevant})
-                        self.qnonrels[q_id].update({i: 0 for i in retrieved - self.qrels[q_id].keys()})
+                        self.judge(q_id, run_keys, gt, question_type)
         return batch
+
+    def judge(self, q_id, run_keys, gt, question_type="String"):
+        """Judge the retrieved passages ``run_keys`` (document ids as strings) of question ``q_id`` that no earlier call judged
+        (reference: search.py:442-457); ``qrels`` / ``qnonrels`` are the record."""
+        self.qrels.setdefault(q_id, {})
+        self.qnonrels.setdefault(q_id, {})
+        retrieved = run_keys - (self.qrels[q_id].keys() | self.qnonrels[q_id].keys())
+        _, relevant = find_relevant(retrieved, gt["original_answer"], gt["answer"], self.reference_kb,
+                                    reference_key=self.reference_key, question_type=question_type,
+                                    passages=self._passage_texts())
+        self.qrels[q_id].update({str(i): 1 for i in relevant})
+        self.qnonrels[q_id].update({i: 0 for i in retrieved - self.qrels[q_id].keys()})
 
 
 class ArrowQueryColumns:
