@@ -765,22 +765,31 @@ int mq_reader_best_spans_f32(const float *start_p_dev, const float *end_p_dev, c
  *   score     of a document for a query = the sequential fp32 sum, in clause order, of weight * impact (multiply, then add: never
  *             fused) over the clauses (term, weight = float(multiplicity) * idf) whose term the document holds
  * Index layout (device): ptr [n_terms + 1] int64, doc [nnz] int32 ascending inside a term, tf [nnz] int32, impact [nnz] fp32.
- * Queries (device): qptr [nq + 1] int32 into cterm [n_clauses] int32 / cweight [n_clauses] fp32, clauses in clause order.
+ * Queries (device): qptr [nq + 1] int32 into cterm [n_clauses] int32 / cweight [n_clauses] fp32, clauses in clause order.  A
+ *   clause whose term id lies outside [0, n_terms) contributes nothing and nothing is read through it (ptr is not indexed with it);
+ *   the same term may recur among a query's clauses, each occurrence is added in its place.
  * mq_bm25_block_rows: documents per scoring workgroup, whose fp32 accumulators live in LDS (MQ_BM25_BLOCK_ROWS).
+ * mq_bm25_clause_batch: clauses of a query whose posting ranges a scoring workgroup searches at once (both scoring kernels); a longer
+ *   query takes several batches, its sum stays the sequential one in clause order.
  * mq_bm25_impacts_f32: fills impact for all nnz postings (again after a change of k1 / b: the index itself stays).
  * mq_topk_rows_f32: exact top-k of every row of a dense fp32 matrix scores [rows, N] of NON-NEGATIVE values (N < 2^31, rows <=
  *   65535): D [rows, k] fp32 / I [rows, k] int64 best first, equal scores by ascending id (descending with MQ_KNN_FLAG_TIE_ID_DESC,
  *   the only flag accepted); an element equal to +0 is not a hit; slots beyond a row's hits are (-inf, -1); id_offset is added to
  *   every id.  Radix select on the key (score bits << 32) | id, integer atomics only: results are bit for bit reproducible.
  *   k <= MQ_KNN_MAX_K (MQ_EUNSUPPORTED beyond); ws: mq_topk_rows_workspace_bytes(rows, k).
+ * mq_topk_rows_launch_info: the geometry of that selection for `rows` rows of N elements (host only, no HIP call; for tests and
+ *   profiles): out[0] = workgroups that share one row, out[1] = histogram passes, out[2 + p] = the key shift of pass p.  MQ_EINVAL
+ *   for the rows / N that mq_topk_rows_f32 refuses, and for out == NULL.
  * mq_bm25_search_f32: scores the nq queries in chunks of mq_bm25_chunk_queries(N, nq, budget_bytes) -- as many as keep the dense
  *   [chunk, N] fp32 score matrix within budget_bytes, at least one -- and selects each chunk's top-k; results do not depend on the
  *   chunking.  ws: mq_bm25_workspace_bytes(N, nq, k, budget_bytes).  Arguments are validated before any HIP call. */
 #define MQ_BM25_BLOCK_ROWS 16384
 int mq_bm25_block_rows(void);
+int mq_bm25_clause_batch(void);
 int mq_bm25_impacts_f32(const int32_t *doc_dev, const int32_t *tf_dev, const uint8_t *code_dev, const float *cache_dev, int64_t nnz,
                         float *impact_dev, void *stream);
 size_t mq_topk_rows_workspace_bytes(int rows, int k);
+int mq_topk_rows_launch_info(int rows, int64_t N, int64_t out[8]);
 int mq_topk_rows_f32(const float *scores_dev, int rows, int64_t N, int k, int flags, int64_t id_offset, float *D_dev,
                      int64_t *I_dev, void *ws_dev, size_t ws_bytes, void *stream);
 int mq_bm25_chunk_queries(int64_t N, int nq, size_t budget_bytes);

@@ -185,7 +185,75 @@ def topk(scores, k, tie_order="id_asc"):
     return (keys >> np.uint64(32)).astype(np.uint32).view(np.float32), out_ids
 
 
+def scores_raw(rest, terms, weights):
+    """Dense fp32 scores of ONE raw clause array as the kernels take it (search_device / search_grid_device, the C ABI): clause by
+    clause in clause order acc[docs] = acc[docs] + float32(w) * impact, nothing de-duplicated (a term that recurs is added again in
+    its place); a term id outside [0, V) or a term without postings does nothing."""
+    acc = np.zeros(rest.N, dtype=np.float32)
+    for t, w in zip(np.asarray(terms).tolist(), np.asarray(weights, dtype=np.float32)):
+        if not 0 <= t < rest.V:
+            continue
+        docs, impact = rest.impacts[t]
+        if len(docs):
+            acc[docs] = acc[docs] + np.float32(w) * impact
+    return acc
+
+
+def search_raw(rest, queries, k, tie_order="id_asc"):
+    """(D, I) of raw clause arrays [(terms, weights)], as Restatement.search."""
+    D = np.full((len(queries), k), -np.inf, dtype=np.float32)
+    I = np.full((len(queries), k), -1, dtype=np.int64)
+    for row, (t, w) in enumerate(queries):
+        d, i = topk(scores_raw(rest, t, w), k, tie_order)
+        D[row, :len(d)], I[row, :len(i)] = d, i
+    return D, I
+
+
 # ---------------------------------------------------------------------------------------------------------------- shared cases
+INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
+# what the clause-batch tests plant at the last clause of a query's first batch, the first clause of its second and its last clause
+CLAUSE_PLANTS = {"every": T_EVERY, "unused": T_UNUSED, "minus1": -1, "V": VOCABULARY_SIZE, "V+7": VOCABULARY_SIZE + 7,
+                 "int32_max": INT32_MAX, "int32_min": INT32_MIN}
+ZERO_WEIGHT_QUERY, LONG_QUERY = 0, 7   # rows of clause_queries(): the weight-0 query, the one of 2 CB + 1 clauses
+
+
+def clause_counts(CB):
+    """Clauses per query of the raw batch, CB = mq_bm25_clause_batch(): the weight-0 query first (so that no longer query starts at
+    a multiple of CB in cterm), then none, one, one short of a batch, a batch, one more, two batches, one more, three and five."""
+    return [1, 1, 0, CB - 1, CB, CB + 1, 2 * CB, 2 * CB + 1, 3 * CB + 5]
+
+
+def plant_positions(count, CB):
+    """Where a query of `count` clauses gets the planted term: CB - 1, CB and its last clause (those it has)."""
+    return sorted({p for p in (CB - 1, CB, count - 1) if 0 <= p < count})
+
+
+def clause_queries(CB, plant, seed=3):
+    """The raw batch [(terms int32, weights fp32)] of clause_counts(CB).  Query j's terms cycle through every third in-vocabulary
+    id from j % 3 on plus the four hand-placed terms (about 172 ids: a term recurs inside a batch and across batches, the three
+    strides together name the whole vocabulary); weights are uniform in [0.1, 3); `plant` (a term id) sits at plant_positions.  Query
+    0 is the single clause (T_EVERY, weight 0): every product is +0, no document is a hit."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for j, count in enumerate(clause_counts(CB)):
+        ids = list(range(j % 3, ZIPF_TERMS, 3)) + [T_EVERY, T_LAST, T_BLOCK_END, T_BLOCK_START]
+        terms = np.array([ids[(7 * j + i) % len(ids)] for i in range(count)], dtype=np.int64)
+        weights = rng.uniform(0.1, 3.0, count).astype(np.float32)
+        if j == ZERO_WEIGHT_QUERY:
+            terms[:], weights[:] = T_EVERY, 0.0
+        else:
+            terms[plant_positions(count, CB)] = plant
+        out.append((terms.astype(np.int32), weights))
+    return out
+
+
+def pack_raw(queries):
+    """(qptr int32 [nq + 1], cterm int32, cweight fp32) of raw clause arrays, the C ABI's layout."""
+    qptr = np.zeros(len(queries) + 1, dtype=np.int32)
+    np.cumsum([len(t) for t, _ in queries], out=qptr[1:])
+    return (qptr, np.concatenate([t for t, _ in queries]).astype(np.int32), np.concatenate([w for _, w in queries]).astype(np.float32))
+
+
 def corpus_sizes(R):
     return (1, R - 1, R + 37, 3 * R + 1)
 

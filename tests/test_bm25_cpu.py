@@ -185,9 +185,78 @@ def test_conditions_of_the_gpu_cases(hip_lib):
     assert len(tied) > 1 and tied.min() < R <= tied.max()
 
 
+def test_conditions_of_the_clause_batch_cases(hip_lib):
+    """What tests/test_bm25_clauses_gpu.py takes for granted, on the restatement alone (CB and R from the library)."""
+    CB, R = hip_lib.mq_bm25_clause_batch(), hip_lib.mq_bm25_block_rows()
+    counts = br.clause_counts(CB)
+    assert counts[br.ZERO_WEIGHT_QUERY] == 1 and counts[br.LONG_QUERY] == 2 * CB + 1
+    assert sorted(counts[1:]) == [0, 1, CB - 1, CB, CB + 1, 2 * CB, 2 * CB + 1, 3 * CB + 5]
+    batches = [-(-c // CB) for c in counts[1:]]                  # batches a workgroup walks for each query
+    assert batches == [1, 0, 1, 1, 2, 2, 3, 4]
+    assert counts[3] < CB == counts[4] < counts[5] and counts[6] == 2 * CB < counts[7] and counts[8] > 3 * CB
+    # the planted positions: the last clause of the first batch, the first clause of the second, the query's last clause
+    assert br.plant_positions(2 * CB + 1, CB) == [CB - 1, CB, 2 * CB]
+    assert (CB - 1) // CB == 0 and CB // CB == 1 and (CB - 2) // CB == 0
+    assert br.plant_positions(CB + 1, CB) == [CB - 1, CB] and br.plant_positions(CB, CB) == [CB - 1]
+    assert br.plant_positions(CB - 1, CB) == [CB - 2] and br.plant_positions(1, CB) == [0] and br.plant_positions(0, CB) == []
+    V = br.VOCABULARY_SIZE
+    assert sorted(br.CLAUSE_PLANTS.values()) == sorted([br.T_EVERY, br.T_UNUSED, -1, V, V + 7, 2 ** 31 - 1, -2 ** 31])
+    rest = br.restated(R + 37, R)
+    assert rest.V == V and rest.doc_freq[br.T_UNUSED] == 0 and rest.doc_freq[br.T_EVERY] == rest.N
+    named = set()
+    for name, plant in br.CLAUSE_PLANTS.items():
+        queries = br.clause_queries(CB, plant)
+        assert [len(t) for t, _ in queries] == counts and all(t.dtype == np.int32 and w.dtype == np.float32 for t, w in queries)
+        qptr, cterm, cweight = br.pack_raw(queries)
+        assert qptr[-1] == len(cterm) == len(cweight) == sum(counts)
+        # in ONE launch no query of a batch or more starts at a multiple of CB in cterm (its batches are not the array's)
+        assert all(qptr[j] % CB for j, c in enumerate(counts) if c >= CB)
+        for j, (t, w) in enumerate(queries):
+            if j == br.ZERO_WEIGHT_QUERY:
+                assert t.tolist() == [br.T_EVERY] and w.tolist() == [0.0]
+                continue
+            at = br.plant_positions(len(t), CB)
+            assert (t[at] == plant).all() and (w >= 0.1).all() and (w < 3).all()
+            rest_of = np.delete(t, at)
+            assert ((rest_of >= 0) & (rest_of < V)).all() and (rest.doc_freq[rest_of] > 0).all()     # in-vocabulary ids
+            named.update(rest_of.tolist())
+            if len(t) > CB:   # a term recurs inside the first batch, and across batches
+                assert len(set(t[:CB].tolist())) < CB and set(t[:CB].tolist()) & set(t[CB:].tolist())
+        # the weight-0 query has no hits: every product is +0
+        assert not br.scores_raw(rest, *queries[br.ZERO_WEIGHT_QUERY]).view(np.uint32).any()
+    assert named >= set(range(br.ZIPF_TERMS)) | {br.T_EVERY, br.T_LAST, br.T_BLOCK_END, br.T_BLOCK_START}
+    # scores_raw: what Restatement.scores gives on de-duplicated clauses, and no de-duplication of its own
+    q = br.queries()[4]
+    terms, weights = zip(*rest.clauses(q))
+    assert np.array_equal(br.scores_raw(rest, terms, weights).view(np.uint32), rest.scores(q).view(np.uint32))
+    twice = br.scores_raw(rest, [br.T_EVERY, br.T_EVERY], [1.5, 1.5])
+    assert np.array_equal(twice, br.scores_raw(rest, [br.T_EVERY, -1, V, br.T_UNUSED, br.T_EVERY], [1.5, 9, 9, 9, 1.5]))
+    assert (twice > br.scores_raw(rest, [br.T_EVERY], [1.5])).all()
+    # the order of the clauses is visible in the bits: a kernel that added the batches (or the clauses) in another order would be seen
+    t, w = br.clause_queries(CB, br.T_EVERY)[br.LONG_QUERY]
+    forward, backward = br.scores_raw(rest, t, w), br.scores_raw(rest, t[::-1], w[::-1])
+    assert (forward.view(np.uint32) != backward.view(np.uint32)).any()
+    swapped = np.concatenate([np.arange(CB, 2 * CB), np.arange(CB), [2 * CB]])          # the first two batches exchanged
+    assert (forward.view(np.uint32) != br.scores_raw(rest, t[swapped], w[swapped]).view(np.uint32)).any()
+    # ... and so is a batch that is skipped
+    assert (forward.view(np.uint32) != br.scores_raw(rest, t[:CB], w[:CB]).view(np.uint32)).any()
+    assert (forward.view(np.uint32) != br.scores_raw(rest, np.delete(t, np.arange(CB, 2 * CB)), np.delete(w, np.arange(CB, 2 * CB))).view(np.uint32)).any()
+
+
 def test_search_entry_validates_before_any_hip_call(hip_lib):
     assert hip_lib.mq_bm25_search_f32(None, None, None, 10, 5, None, None, None, 1, 5, 0, 0, None, None, None, 0, 0, None) == -1
     assert hip_lib.mq_topk_rows_f32(None, 1, 10, 5, 0, 0, None, None, None, 0, None) == -1
     assert hip_lib.mq_topk_rows_workspace_bytes(4, 2049) == 0 and hip_lib.mq_topk_rows_workspace_bytes(4, 2048) > 0
     assert hip_lib.mq_bm25_chunk_queries(1000, 37, 1000 * 4 * 5) == 5 and hip_lib.mq_bm25_chunk_queries(1000, 37, 0) == 1
     assert hip_lib.mq_bm25_chunk_queries(1000, 37, 1 << 30) == 37
+    assert hip_lib.mq_bm25_clause_batch() >= 2
+    import ctypes
+    out = (ctypes.c_int64 * 8)()
+    assert hip_lib.mq_topk_rows_launch_info(4, 70_001, out) == 0
+    assert list(out) == [5, 6, 53, 42, 32, 21, 10, 0]                    # 5 workgroups a row, six passes of 11 / 11 / 10 / 11 / 11 / 10 bits
+    assert hip_lib.mq_topk_rows_launch_info(1, 1, out) == 0 and out[0] == 1
+    assert hip_lib.mq_topk_rows_launch_info(2048, 17_000, out) == 0 and out[0] == 1
+    for rows, N in ((0, 10), (65536, 10), (1, 0), (1, 1 << 31)):          # what mq_topk_rows_f32 refuses
+        assert hip_lib.mq_topk_rows_launch_info(rows, N, out) == -1
+        assert hip_lib.mq_topk_rows_f32(1, rows, N, 5, 0, 0, 1, 1, 1, 1 << 40, None) == -1
+    assert hip_lib.mq_topk_rows_launch_info(1, 10, None) == -1

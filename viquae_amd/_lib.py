@@ -115,8 +115,10 @@ SIGNATURES = {
     "mq_reader_log_softmax_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mq_reader_best_spans_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mq_bm25_block_rows": (c_int, []),
+    "mq_bm25_clause_batch": (c_int, []),
     "mq_bm25_impacts_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "mq_topk_rows_workspace_bytes": (c_sz, [c_int, c_int]),
+    "mq_topk_rows_launch_info": (c_int, [c_int, c_i64, ctypes.POINTER(c_i64)]),
     "mq_topk_rows_f32": (c_int, [c_ptr, c_int, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_sz, c_ptr]),
     "mq_bm25_chunk_queries": (c_int, [c_i64, c_int, c_sz]),
     "mq_bm25_workspace_bytes": (c_sz, [c_i64, c_int, c_int, c_sz]),

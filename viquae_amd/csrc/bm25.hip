@@ -41,8 +41,8 @@ constexpr int PASSES = 6;
 constexpr int ROWS_PER_WG = TT * 16;   // least share of a row worth a workgroup of its own
 constexpr int MAX_SPLIT = 64;
 
-__device__ __forceinline__ int pass_shift(int p) { return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0; }
-__device__ __forceinline__ int pass_bits(int p) { return (p == 2 || p == 5) ? 10 : 11; }
+__host__ __device__ __forceinline__ int pass_shift(int p) { return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0; }
+__host__ __device__ __forceinline__ int pass_bits(int p) { return (p == 2 || p == 5) ? 10 : 11; }
 
 __global__ __launch_bounds__(256) void bm25_impact_kernel(const int32_t* __restrict__ doc, const int32_t* __restrict__ tf,
                                                           const uint8_t* __restrict__ code, const float* __restrict__ cache,
@@ -365,17 +365,22 @@ inline TopkLayout topk_layout(int rows, int k) {
     return l;
 }
 
-int topk_rows(const float* scores, int rows, int64_t N, int k, int flags, int64_t id_offset, float* D, int64_t* I, char* ws,
-              hipStream_t st) {
-    const TopkLayout l = topk_layout(rows, k);
-    TopkArgs a;
-    a.scores = scores; a.N = N; a.k = k; a.id_desc = (flags & MQ_KNN_FLAG_TIE_ID_DESC) ? 1 : 0;
+// workgroups that share one row of N elements when `rows` rows are selected at once
+inline int topk_split(int rows, int64_t N) {
     int64_t split = (N + ROWS_PER_WG - 1) / ROWS_PER_WG;
     const int64_t fill = (2048 + rows - 1) / rows;  // enough workgroups for every CU, not more
     if (split > fill) split = fill;
     if (split > MAX_SPLIT) split = MAX_SPLIT;
     if (split < 1) split = 1;
-    a.split = (int)split;
+    return (int)split;
+}
+
+int topk_rows(const float* scores, int rows, int64_t N, int k, int flags, int64_t id_offset, float* D, int64_t* I, char* ws,
+              hipStream_t st) {
+    const TopkLayout l = topk_layout(rows, k);
+    TopkArgs a;
+    a.scores = scores; a.N = N; a.k = k; a.id_desc = (flags & MQ_KNN_FLAG_TIE_ID_DESC) ? 1 : 0;
+    a.split = topk_split(rows, N);
     a.hist = reinterpret_cast<uint32_t*>(ws + l.hist);
     a.count = reinterpret_cast<uint32_t*>(ws + l.count);
     a.cand = reinterpret_cast<uint64_t*>(ws + l.cand);
@@ -420,6 +425,8 @@ extern "C" {
 
 int mq_bm25_block_rows(void) { return R; }
 
+int mq_bm25_clause_batch(void) { return CB; }
+
 int mq_bm25_impacts_f32(const int32_t* doc_dev, const int32_t* tf_dev, const uint8_t* code_dev, const float* cache_dev,
                         int64_t nnz, float* impact_dev, void* stream) {
     if (nnz < 0) return MQ_EINVAL;
@@ -435,6 +442,14 @@ int mq_bm25_impacts_f32(const int32_t* doc_dev, const int32_t* tf_dev, const uin
 size_t mq_topk_rows_workspace_bytes(int rows, int k) {
     if (rows < 1 || rows > MAX_ROWS_PER_CALL || k < 1 || k > MQ_KNN_MAX_K) return 0;
     return topk_layout(rows, k).total;
+}
+
+int mq_topk_rows_launch_info(int rows, int64_t N, int64_t out[8]) {
+    if (!out || rows < 1 || rows > MAX_ROWS_PER_CALL || N < 1 || N > 0x7fffffffLL) return MQ_EINVAL;
+    out[0] = topk_split(rows, N);
+    out[1] = PASSES;
+    for (int p = 0; p < PASSES; ++p) out[2 + p] = pass_shift(p);
+    return MQ_OK;
 }
 
 int mq_topk_rows_f32(const float* scores_dev, int rows, int64_t N, int k, int flags, int64_t id_offset, float* D_dev,
