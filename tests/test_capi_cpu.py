@@ -94,3 +94,69 @@ def test_streaming_kernels_do_not_spill():
     expected.add("_ZN12_GLOBAL__N_120screen_small8_kernelILi12ELb1EEEvNS_9SmallArgsE")  # the ROWTERM instance
     assert set(watched) == expected and len(expected) == 14, sorted(watched)
     assert all(v == 0 for v in watched.values()), {k: v for k, v in watched.items() if v}
+
+
+_FAILING_LAUNCHES = r"""
+import ctypes, json
+from viquae_amd import _lib
+lib = _lib.load()
+buf = ctypes.create_string_buffer(4096)
+p = (ctypes.addressof(buf) + 15) & ~15          # a non-null, 16-byte-aligned placeholder: without a device nothing reads it
+calls = {
+    # conv.hip: a plain launch, and one that raises the kernel's dynamic LDS first
+    "mq_head_prep_f16": lambda: lib.mq_head_prep_f16(p, 1, 1, 32, p, p, p, p, None),
+    "mq_conv3x3_pair_f32": lambda: lib.mq_conv3x3_pair_f32(p, p, 1, 2, 2, 32, 1, p, p, 64, p, p, None, None, None, None, p, p, p, 0, None),
+    # resnet.hip: likewise
+    "mq_pool_hw_f32": lambda: lib.mq_pool_hw_f32(p, 1, 4, 8, 0, p, None),
+    "mq_conv1x1_pair_f32": lambda: lib.mq_conv1x1_pair_f32(p, p, 1, 2, 2, 32, 1, p, p, 64, p, None, 0, p, None, None, p, 0, None),
+    # clip_resnet.hip, diag.hip
+    "mq_avgpool2x2_pair_f32": lambda: lib.mq_avgpool2x2_pair_f32(p, p, 1, 2, 2, 32, p, p, None),
+    "mq_diag_mfma_bf16_dot": lambda: lib.mq_diag_mfma_bf16_dot(p, p, 16, p, None),
+}
+out = {"initial": lib.mq_last_hip_error()}
+for name, call in calls.items():
+    lib.mq_internal_set_hip_error(0)
+    out[name] = [call(), lib.mq_last_hip_error()]
+print(json.dumps(out))
+"""
+
+
+def test_hip_failures_are_recorded():
+    """MQ_EHIP promises "see mq_last_hip_error()": every entry reports a failing HIP call through MQ_HIP / mq_launch_status
+    (csrc/host_check.h), which record the error.  Without a device every launch fails, so entries of conv.hip, resnet.hip,
+    clip_resnet.hip and diag.hip -- whose bare `hipGetLastError() == hipSuccess ? ...` returns recorded nothing -- are called with
+    arguments that clear validation, in a child process (the error is thread-local and starts at 0)."""
+    import json
+    import subprocess
+    import sys
+    import pytest
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("needs a machine without a GPU: there every launch fails")
+    from viquae_amd import build
+    build.build()
+    res = subprocess.run([sys.executable, "-c", _FAILING_LAUNCHES], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    out = json.loads(res.stdout.strip().splitlines()[-1])
+    assert out.pop("initial") == 0
+    assert len(out) == 6
+    for name, (code, err) in out.items():
+        assert code == -3 and err != 0, (name, code, err)   # MQ_EHIP, and the hipError_t behind it
+
+
+def test_shared_helpers_are_defined_once():
+    """The device helpers that define the library's data layout (csrc/device_common.h, csrc/x3_tile.h) and the HIP error path
+    (csrc/host_check.h) have one definition: no translation unit grows its own copy again."""
+    csrc = os.path.join(ROOT, "viquae_amd", "csrc")
+    names = "pair_index|split1|split8|split4|split_bits|join8|store_split_pair|lds_addr_of|dma16s|dma16v|wave_sum|wave_min|wave_max"
+    units = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".inc")))
+    assert len(units) >= 16
+    for f in units:
+        src = open(os.path.join(csrc, f)).read()
+        m = re.search(r"^[ \t]*(?:template\s*<[^>]*>\s*)?(?:static\s+|inline\s+|__device__\s+|__host__\s+|__forceinline__\s+)+"
+                      r"[\w:<>\*&\s]+?\b(" + names + r")\s*\([^;{]*\)\s*\{", src, flags=re.M)
+        assert not m, f"{f} defines {m.group(1)}: it belongs to the shared headers"
+        assert not re.search(r"typedef[^;]*\b(bf16x8_t|bf16x4_t|f32x16|lds_char)\s*(__attribute__[^;]*)?;", src), f"{f}: a shared typedef"
+        assert not re.search(r"#\s*define\s+\w+_HIP\(call\)", src), f"{f} defines its own HIP check macro"
+        assert "hipGetLastError() == hipSuccess" not in src, f"{f} returns a launch status without recording the error"
+        assert "mq_internal_set_hip_error(int" not in src or f == "knn.hip", f"{f} re-declares mq_internal_set_hip_error"

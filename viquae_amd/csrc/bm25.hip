@@ -20,16 +20,9 @@
 #include <math.h>
 
 #include "../../include/meerqat_hip.h"
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "host_check.h"
 
 namespace {
-
-#define BM25_HIP(call)                                                                \
-    do {                                                                              \
-        hipError_t _e = (call);                                                       \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
 
 constexpr int R = MQ_BM25_BLOCK_ROWS;  // documents per scoring workgroup: 16,384 fp32 accumulators = 64 KiB of LDS
 constexpr int ST = 512;                // threads of a scoring workgroup
@@ -386,13 +379,12 @@ int topk_rows(const float* scores, int rows, int64_t N, int k, int flags, int64_
     a.cand = reinterpret_cast<uint64_t*>(ws + l.cand);
     a.kpad = kpad_of(k);
     a.D = D; a.I = I; a.id_offset = id_offset;
-    BM25_HIP(hipMemsetAsync(ws, 0, l.cand, st));  // histograms and counters
+    MQ_HIP(hipMemsetAsync(ws, 0, l.cand, st));  // histograms and counters
     const dim3 grid(a.split, rows);
     for (int p = 0; p < PASSES; ++p) hipLaunchKernelGGL(topk_hist_kernel, grid, dim3(TT), 0, st, a, p);
     hipLaunchKernelGGL(topk_gather_kernel, grid, dim3(TT), 0, st, a);
     hipLaunchKernelGGL(topk_sort_kernel, dim3(rows), dim3(TT), 0, st, a);
-    BM25_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 constexpr int MAX_ROWS_PER_CALL = 65535;  // gridDim.y
@@ -435,8 +427,7 @@ int mq_bm25_impacts_f32(const int32_t* doc_dev, const int32_t* tf_dev, const uin
     const int64_t blocks = (nnz + 255) / 256;
     hipLaunchKernelGGL(bm25_impact_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream,
                        doc_dev, tf_dev, code_dev, cache_dev, impact_dev, nnz);
-    BM25_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 size_t mq_topk_rows_workspace_bytes(int rows, int k) {
@@ -499,7 +490,7 @@ int mq_bm25_search_f32(const int64_t* ptr_dev, const int32_t* doc_dev, const flo
         const int n = nq - q0 < chunk ? nq - q0 : chunk;
         hipLaunchKernelGGL(bm25_score_kernel, dim3(blocks, n), dim3(ST), 0, st, ptr_dev, doc_dev, impact_dev, N, n_terms,
                            qptr_dev + q0, cterm_dev, cweight_dev, scores);
-        BM25_HIP(hipGetLastError());
+        MQ_HIP(hipGetLastError());
         const int rc = topk_rows(scores, n, N, k, flags, id_offset, D_dev + (int64_t)q0 * k, I_dev + (int64_t)q0 * k, sel, st);
         if (rc != MQ_OK) return rc;
     }
@@ -565,7 +556,7 @@ int mq_bm25_search_grid_f32(const int64_t* ptr_dev, const int32_t* doc_dev, cons
                 case 4: launch_grid<4>(a, caches, gt, q0, n, scores, st); break;
                 default: launch_grid<8>(a, caches, gt, q0, n, scores, st); break;
             }
-            BM25_HIP(hipGetLastError());
+            MQ_HIP(hipGetLastError());
             if (n == nq) {  // the tile's rows (setting, query) are consecutive rows of D / I: one selection over all of them
                 const int rc = topk_rows(scores, gt * n, N, k, flags, id_offset, D_dev + (int64_t)g0 * nq * k,
                                          I_dev + (int64_t)g0 * nq * k, sel, st);
@@ -577,9 +568,9 @@ int mq_bm25_search_grid_f32(const int64_t* ptr_dev, const int32_t* doc_dev, cons
             const int rc = topk_rows(scores, gt * n, N, k, flags, id_offset, stage_D, stage_I, sel, st);
             if (rc != MQ_OK) return rc;
             const int64_t at = ((int64_t)g0 * nq + q0) * k;
-            BM25_HIP(hipMemcpy2DAsync(D_dev + at, (size_t)nq * k * sizeof(float), stage_D, (size_t)n * k * sizeof(float),
+            MQ_HIP(hipMemcpy2DAsync(D_dev + at, (size_t)nq * k * sizeof(float), stage_D, (size_t)n * k * sizeof(float),
                                       (size_t)n * k * sizeof(float), gt, hipMemcpyDeviceToDevice, st));
-            BM25_HIP(hipMemcpy2DAsync(I_dev + at, (size_t)nq * k * sizeof(int64_t), stage_I, (size_t)n * k * sizeof(int64_t),
+            MQ_HIP(hipMemcpy2DAsync(I_dev + at, (size_t)nq * k * sizeof(int64_t), stage_I, (size_t)n * k * sizeof(int64_t),
                                       (size_t)n * k * sizeof(int64_t), gt, hipMemcpyDeviceToDevice, st));
         }
     }

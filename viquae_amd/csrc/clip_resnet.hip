@@ -1,6 +1,7 @@
 // clip_resnet.hip -- what openai-clip's ModifiedResNet (the `clip-RN50` column) needs beyond conv.hip and resnet.hip, for gfx950.  Same
-// conventions: NHWC, an activation that only feeds convolutions is a split-bf16 (hi, lo) pair in PAIR LAYOUT ([row / 256][col / 32][256]
-// [32]), BatchNorms folded on the host.  All four kernels run on the vector ALU and are bound by memory traffic, not arithmetic.
+// conventions: NHWC, an activation that only feeds convolutions is a split-bf16 (hi, lo) pair in PAIR LAYOUT (device_common.h, with
+// the split, the join and the wave reductions), BatchNorms folded on the host.  All four kernels run on the vector ALU and are bound by
+// memory traffic, not arithmetic.
 //   stem3x3s2_kernel      conv 3 x 3 / 2 (3 -> 32, pad 1) + folded bn1 + ReLU: fp32 NCHW pixels -> the pair.  K = 27 has no matrix-pipe shape.
 //   avgpool2x2_kernel     AvgPool2d(2) on a pair -> pair (the stem's pool, the pool in front of a strided block's conv3, the shortcut's).
 //   attn_tokens_kernel    AttentionPool2d's token matrix: [mean over HW | the HW pixels] + positional embedding -> pair, and the mean
@@ -10,29 +11,12 @@
 #include <stdint.h>
 
 #include "../../include/meerqat_hip.h"
+#include "device_common.h"
+#include "host_check.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-// element (row, col) of a pair [M, K] (encoder.hip, PAIR LAYOUT)
-__device__ __forceinline__ size_t pair_index(size_t row, int col, int K) {
-    return ((row >> 8) * (size_t)(K >> 5) + (size_t)(col >> 5)) * (256 * 32) + ((row & 255) << 5) + (size_t)(col & 31);
-}
-
-__device__ __forceinline__ void split8(const float (&t)[8], bf16x8_t& h8, bf16x8_t& l8) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h = (__bf16)t[e];
-        h8[e] = h;
-        l8[e] = (__bf16)(t[e] - (float)h);
-    }
-}
-
-__device__ __forceinline__ void join8(const bf16x8_t& h8, const bf16x8_t& l8, float (&t)[8]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = (float)h8[e] + (float)l8[e];   // exact in fp32: |lo| <= ulp(hi) / 2, 8 + 8 significant bits
-}
+using namespace mq_dev;
 
 // ---- the stem's first convolution: 3 x 3, stride 2, padding 1, 3 -> 32 channels, + bias (bn1 folded), ReLU --------------------------
 // A thread = 8 output channels x 4 adjacent output pixels of one row: per (kh, c) it reads the 9 input pixels 2 ow0 - 1 ... 2 ow0 + 7 of
@@ -193,17 +177,6 @@ __global__ __launch_bounds__(64) void attn_tokens_kernel(const float* __restrict
 //   m = max s_t;  p_t = expf(s_t - m);  l = sum p_t (each lane sums its t = lane, lane + 64, ... in that order, then the butterfly);
 //   o[d] = (sum over t = 0 ... T - 1, in that order, of p_t v_t[d]) / l  -> split pair over [B, C].
 // A wave reads 256 contiguous bytes of K, then of V, per key.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, s, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(64) void attn_single_query_kernel(const float* __restrict__ q, const float* __restrict__ kv,
                                                                unsigned short* __restrict__ Oh, unsigned short* __restrict__ Ol, int T,
                                                                int heads, float scale) {
@@ -234,7 +207,8 @@ __global__ __launch_bounds__(64) void attn_single_query_kernel(const float* __re
     float o = 0.f;
     for (int t = 0; t < T; ++t) o += sc[t] * v0[(size_t)t * (2 * C)];
     o /= l;
-    const __bf16 hi = (__bf16)o, lo = (__bf16)(o - (float)hi);
+    __bf16 hi, lo;
+    split1(o, hi, lo);
     const size_t at = pair_index(b, h * 64 + lane, C);
     Oh[at] = __builtin_bit_cast(unsigned short, hi);
     Ol[at] = __builtin_bit_cast(unsigned short, lo);
@@ -254,7 +228,7 @@ int mq_clip_stem_conv3x3s2_f32(const float* x_dev, int B, int H, int W, const fl
     if ((units + 63) / 64 > 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
     hipLaunchKernelGGL(stem3x3s2_kernel, dim3((unsigned)((units + 63) / 64)), dim3(256), 0, (hipStream_t)stream, x_dev, wt_dev, bias_dev,
                        (unsigned short*)Ph_dev, (unsigned short*)Pl_dev, B, H, W);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_avgpool2x2_pair_f32(const uint16_t* Xh_dev, const uint16_t* Xl_dev, int B, int H, int W, int C, uint16_t* Ph_dev, uint16_t* Pl_dev,
@@ -270,7 +244,7 @@ int mq_avgpool2x2_pair_f32(const uint16_t* Xh_dev, const uint16_t* Xl_dev, int B
     hipLaunchKernelGGL(avgpool2x2_kernel, dim3((unsigned)(chunks / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)Xh_dev, (const unsigned short*)Xl_dev, (unsigned short*)Ph_dev, (unsigned short*)Pl_dev, H, W,
                        C, (unsigned)M);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_attnpool_tokens_f32(const float* Y_dev, int B, int HW, int C, const float* pos_dev, uint16_t* Th_dev, uint16_t* Tl_dev,
@@ -284,7 +258,7 @@ int mq_attnpool_tokens_f32(const float* Y_dev, int B, int HW, int C, const float
     if ((threads + 63) / 64 > 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
     hipLaunchKernelGGL(attn_tokens_kernel, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, (hipStream_t)stream, Y_dev, pos_dev,
                        (unsigned short*)Th_dev, (unsigned short*)Tl_dev, (unsigned short*)Qh_dev, (unsigned short*)Ql_dev, B, HW, C);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_attention_single_query_f32(const float* q_dev, const float* kv_dev, int B, int T, int heads, int head_dim, float scale,
@@ -295,7 +269,7 @@ int mq_attention_single_query_f32(const float* q_dev, const float* kv_dev, int B
     if ((size_t)B * heads > 0x7FFFFFFFull || (size_t)B * T >= 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
     hipLaunchKernelGGL(attn_single_query_kernel, dim3((unsigned)((size_t)B * heads)), dim3(64), (size_t)T * sizeof(float),
                        (hipStream_t)stream, q_dev, kv_dev, (unsigned short*)Oh_dev, (unsigned short*)Ol_dev, T, heads, scale);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 }  // extern "C"

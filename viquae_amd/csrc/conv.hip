@@ -8,7 +8,7 @@
 //                         elementwise PRE-operations on the way -- PReLU (per-channel slope) of the producing layer, then the
 //                         BatchNorm that stands IN FRONT of the convolution in an IBasicBlock (bn1: per-channel scale / shift,
 //                         exact at the zero-padded border, where folding the shift into the convolution's bias is not) -- and
-//                         writes the (hi, lo) bf16 pair in the GEMM's PAIR LAYOUT ([row / 256][col / 32][256][32]): the GEMM
+//                         writes the (hi, lo) bf16 pair in the GEMM's PAIR LAYOUT (device_common.h: pair_index, the split): the GEMM
 //                         streams it by LDS-DMA and converts nothing.  BatchNorms BEHIND a convolution are folded into its
 //                         weights and bias on the host (exact).
 //   warp_affine_kernel    cv2.warpAffine(image, M, (112, 112), borderValue=0) -- OpenCV's fixed-point bilinear remap as
@@ -24,26 +24,25 @@
 // plus stem_conv_f16_kernel, conv1x1_f16_kernel (the strided downsample) and head_prep_f16_kernel (bn2 -> the head GEMM's pair).
 // Neither OpenCV, scikit-image nor arcface_torch is vendored by the reference or installable here: this path is "parity unpinned"
 // (oracle/arcface.py restates the published algorithms).
+// device_common.h holds the pair layout, the split and the LDS-DMA pieces; x3_tile.h the tile -> XCD mapping and the three-product K
+// step this file shares with resnet.hip; host_check.h the one HIP error path.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "../../include/meerqat_hip.h"
-#include "launch_attr.h"
+#include "host_check.h"
+#include "x3_tile.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+using namespace mq_dev;
+
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
 // r(): round to fp16 and back -- v_cvt_f16_f32, round to nearest even, overflow to +-inf (Tensor.half())
 __device__ __forceinline__ float rh(float x) { return (float)(_Float16)x; }
-
-// element (row, col) of a pair [M, K] (encoder.hip, PAIR LAYOUT)
-__device__ __forceinline__ size_t pair_index(size_t row, int col, int K) {
-    return ((row >> 8) * (size_t)(K >> 5) + (size_t)(col >> 5)) * (256 * 32) + ((row & 255) << 5) + (size_t)(col & 31);
-}
 
 __device__ __forceinline__ float pre_op(float x, int c, const float* __restrict__ slope, const float* __restrict__ scale,
                                         const float* __restrict__ shift) {
@@ -104,12 +103,7 @@ __global__ __launch_bounds__(256) void im2col_split_kernel(const float* __restri
         }
     }
     bf16x8_t h8, l8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        h8[j] = h;
-        l8[j] = (__bf16)(v[j] - (float)h);
-    }
+    split8(v, h8, l8);
     const size_t at = pair_index(row, col0, Kpad);
     *reinterpret_cast<bf16x8_t*>(Ah + at) = h8;
     *reinterpret_cast<bf16x8_t*>(Al + at) = l8;
@@ -129,22 +123,6 @@ __global__ __launch_bounds__(256) void im2col_split_kernel(const float* __restri
 // Tiles: 16 waves, each 64 rows x WN columns; RG row groups x 16 / RG column groups: 256 x 256 (RG 4, WN 64), 512 x 128 (8, 64),
 // 256 x 128 (4, 32), 512 x 64 (8, 32) -- the 64- / 128-channel stages no longer pay for 256-column tiles.
 constexpr int EP_PRELU_PAIR = 0, EP_RESIDUAL_AFFINE = 1;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(unsigned long)(lds_char*)p; }
-// one 1-KiB LDS-DMA piece, LDS destination lds_dst (wave-uniform) + lane * 16: wave-uniform base + per-lane byte offset ...
-__device__ __forceinline__ void dma16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// ... or a 64-bit source address per lane (the gather)
-__device__ __forceinline__ void dma16v(const void* lane_ptr, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_ptr), "s"(lds_dst) : "memory");
-}
 
 struct ConvArgs {
     const unsigned short *Xh, *Xl;  // input pair, PAIR LAYOUT over [B * H * W, C]
@@ -199,14 +177,8 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w / CG, wc = w % CG;
-    // workgroup b runs on XCD b & 7.  Each XCD takes a CONTIGUOUS range of row blocks (per = ceil(ntm / 8) of them) and all
-    // column tiles of a row block: the tiles its CUs hold at one time are neighbours in the image, so the halo rows two row blocks
-    // share (2 of a 512-pixel tile's 4.6 image rows at 112 x 112) and a row block's A rows are fetched into that XCD's L2 once
-    const int b = (int)blockIdx.x;
-    const int per = (a.ntm + 7) >> 3;
-    const int mt = __builtin_amdgcn_readfirstlane((b & 7) * per + (b >> 3) / a.ntn);
-    const int nt = __builtin_amdgcn_readfirstlane((b >> 3) % a.ntn);
-    if ((b >> 3) / a.ntn >= per || mt >= a.ntm) return;
+    int mt, nt;
+    if (!xcd_tile((int)blockIdx.x, a.ntm, a.ntn, &mt, &nt)) return;
     const int m0 = mt * MT, n0 = nt * NT;
     const int CB = a.C >> 5, nk = 9 * CB;
 
@@ -301,36 +273,8 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
 #pragma unroll
                     for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[x], wh[y], acc[x][y], 0, 0, 0);
             }
-            stage ^= 1;
-            continue;
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int o = ((2 * m + kg) ^ sww) * 16;
-            bf16x8_t ah[2], al[2], wh[NF], wl[NF];
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                ah[x] = *reinterpret_cast<const bf16x8_t*>(as + x * 32 * 64 + o);
-                al[x] = *reinterpret_cast<const bf16x8_t*>(as + A_BYTES + x * 32 * 64 + o);
-            }
-#pragma unroll
-            for (int y = 0; y < NF; ++y) {
-                wh[y] = *reinterpret_cast<const bf16x8_t*>(ws + y * 32 * 64 + o);
-                wl[y] = *reinterpret_cast<const bf16x8_t*>(ws + W_BYTES + y * 32 * 64 + o);
-            }
-            // per accumulator: lo.hi, hi.lo, hi.hi -- the order of gemm_nt_x3s_kernel
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[x], wh[y], acc[x][y], 0, 0, 0);
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[x], wl[y], acc[x][y], 0, 0, 0);
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[x], wh[y], acc[x][y], 0, 0, 0);
+        } else {
+            x3_step<NF>(as, ws, A_BYTES, W_BYTES, kg, sww, acc);  // per accumulator: lo.hi, hi.lo, hi.hi
         }
         stage ^= 1;
     }
@@ -338,6 +282,8 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
     // ---- epilogue: one 32 x 32 accumulator at a time through LDS (4 KiB per wave), so that a lane ends up with eight consecutive
     // columns of one row: 16-byte loads and stores.  Bias (and PReLU) in the accumulator layout (one column per lane); residual,
     // affine and split after the transposition: per element the operations of the explicit path, in its order.
+    // The walk is spelled out in each kernel that has it (here, conv.hip, resnet.hip, encoder.hip): shared as one function that takes
+    // the per-element operations as functors, it changes the kernels' assembly.
     __syncthreads();  // every wave has read its last operands
     float* Ot = reinterpret_cast<float*>(smem) + w * 1024;
 #pragma unroll
@@ -392,12 +338,7 @@ __global__ __launch_bounds__(1024) void conv3x3_x3s_kernel(const ConvArgs a) {
                     if (pair_out) {
                         const float t[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
                         bf16x8_t h8, l8;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const __bf16 h = (__bf16)t[e];
-                            h8[e] = h;
-                            l8[e] = (__bf16)(t[e] - (float)h);
-                        }
+                        split8(t, h8, l8);
                         const size_t pt = pair_index((size_t)gm, gn, a.N);
                         *reinterpret_cast<bf16x8_t*>(a.Ph + pt) = h8;
                         *reinterpret_cast<bf16x8_t*>(a.Pl + pt) = l8;
@@ -435,6 +376,7 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w >> 1, wc = w & 1;
+    // xcd_tile()'s mapping, kept in its local form: through the helper, one commutative add of this kernel's assembly swaps its operands
     const int b = (int)blockIdx.x;
     const int per = (a.ntm + 7) >> 3;
     const int mt = __builtin_amdgcn_readfirstlane((b & 7) * per + (b >> 3) / a.ntn);
@@ -557,7 +499,7 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the zero-page requests past the end still target LDS
     __syncthreads();
 
-    // ---- epilogue: conv3x3_x3s_kernel's, for one 32 x 32 accumulator
+    // ---- epilogue: conv3x3_x3s_kernel's, for one 32 x 32 accumulator (spelled out for the same reason)
     float* Ot = reinterpret_cast<float*>(smem) + w * 1024;
     {
         const int col = n0 + 32 * wc + i;
@@ -608,12 +550,7 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
                 if (pair_out) {
                     const float t[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
                     bf16x8_t h8, l8;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const __bf16 hb = (__bf16)t[e];
-                        h8[e] = hb;
-                        l8[e] = (__bf16)(t[e] - (float)hb);
-                    }
+                    split8(t, h8, l8);
                     const size_t pt = pair_index((size_t)gm, gn, a.N);
                     *reinterpret_cast<bf16x8_t*>(a.Ph + pt) = h8;
                     *reinterpret_cast<bf16x8_t*>(a.Pl + pt) = l8;
@@ -623,12 +560,6 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(const ConvArgs a) {
     }
 }
 
-#define CONV_HIP(call)                                  \
-    do {                                                \
-        hipError_t _e = (call);                         \
-        if (_e != hipSuccess) return MQ_EHIP;           \
-    } while (0)
-
 template <int RG, int WN, int EP, bool F16 = false>
 int launch_conv3x3(ConvArgs a, hipStream_t st) {
     constexpr int CG = 16 / RG, MT = 64 * RG, NT = WN * CG, NARR = F16 ? 1 : 2;
@@ -637,9 +568,9 @@ int launch_conv3x3(ConvArgs a, hipStream_t st) {
     a.ntm = (a.M + MT - 1) / MT;
     a.ntn = a.N / NT;
     const int ntiles = ((a.ntm + 7) >> 3) * 8 * a.ntn;
-    MQ_DYNAMIC_LDS_WITH(CONV_HIP, LDS, conv3x3_x3s_kernel<RG, WN, EP, F16>);
+    MQ_DYNAMIC_LDS(LDS, conv3x3_x3s_kernel<RG, WN, EP, F16>);
     hipLaunchKernelGGL((conv3x3_x3s_kernel<RG, WN, EP, F16>), dim3((unsigned)ntiles), dim3(1024), LDS, st, a);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 template <int EP, bool F16 = false>
@@ -648,9 +579,9 @@ int launch_conv3x3_patch(ConvArgs a, hipStream_t st) {
     a.ntm = (a.M + PT_MT - 1) / PT_MT;
     a.ntn = a.N / PT_NT;
     const int ntiles = ((a.ntm + 7) >> 3) * 8 * a.ntn;
-    MQ_DYNAMIC_LDS_WITH(CONV_HIP, LDS, conv3x3_patch_kernel<EP, F16>);
+    MQ_DYNAMIC_LDS(LDS, conv3x3_patch_kernel<EP, F16>);
     hipLaunchKernelGGL((conv3x3_patch_kernel<EP, F16>), dim3((unsigned)ntiles), dim3(1024), LDS, st, a);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 template <int EP, bool F16 = false>
@@ -773,6 +704,7 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const float* __restri
         for (int j = 0; j < 8; ++j) {
             float v = acc[p][j];
             v = v >= 0.f ? v : v * sl[j];
+            // split1() twice, kept in its local form: through the helper this kernel's instruction schedule changes
             const __bf16 dhi = (__bf16)v;
             dh8[j] = dhi;
             dl8[j] = (__bf16)(v - (float)dhi);
@@ -997,7 +929,7 @@ int mq_im2col_split_f32(const float* x_dev, int B, int H, int W, int C, int nchw
     hipLaunchKernelGGL(im2col_split_kernel, dim3((unsigned)(Kpad / 32), gy, gz), dim3(256), 0, (hipStream_t)stream, x_dev, B, H, W, C,
                        nchw, KH, KW, stride, pad, Ho, Wo, prelu_slope_dev, scale_dev, shift_dev, (unsigned short*)Ah_dev,
                        (unsigned short*)Al_dev, Kpad);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_conv3x3_pair_f32(const uint16_t* Xh_dev, const uint16_t* Xl_dev, int B, int H, int W, int C, int stride, const uint16_t* Wh_dev,
@@ -1022,7 +954,7 @@ int mq_stem_conv3x3_f32(const float* x_dev, int B, int H, int W, const float* wt
     hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)((quads + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, wt_dev, bias_dev,
                        prelu_slope_dev, scale_dev, shift_dev, (unsigned short*)Ph_dev, (unsigned short*)Pl_dev, (unsigned short*)Dh_dev,
                        (unsigned short*)Dl_dev, B, H, W);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_conv3x3_f16(const uint16_t* X_dev, int B, int H, int W, int C, int stride, const uint16_t* Wt_dev, int N, const float* post_scale_dev,
@@ -1046,7 +978,7 @@ int mq_stem_conv3x3_f16(const float* x_dev, int B, int H, int W, const float* wt
     hipLaunchKernelGGL(stem_conv_f16_kernel, dim3((unsigned)((quads + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, wt_dev,
                        post_scale_dev, post_shift_dev, prelu_slope_dev, scale_dev, shift_dev, (unsigned short*)P_dev, (unsigned short*)D_dev,
                        B, H, W);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_conv1x1_f16(const uint16_t* X_dev, int B, int H, int W, int C, int stride, const uint16_t* Wt_dev, int N, const float* post_scale_dev,
@@ -1060,7 +992,7 @@ int mq_conv1x1_f16(const uint16_t* X_dev, int B, int H, int W, int C, int stride
     hipLaunchKernelGGL(conv1x1_f16_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(N / 64)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)X_dev, H, W, C, stride, Ho, Wo, (int)M, (const unsigned short*)Wt_dev, N, post_scale_dev,
                        post_shift_dev, (unsigned short*)Y_dev);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_head_prep_f16(const uint16_t* X_dev, int B, int HW, int C, const float* scale_dev, const float* shift_dev, uint16_t* Ah_dev,
@@ -1071,7 +1003,7 @@ int mq_head_prep_f16(const uint16_t* X_dev, int B, int HW, int C, const float* s
     if ((size_t)HW * C >= 0x7FFFFFFFull || (threads + 255) / 256 > 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
     hipLaunchKernelGGL(head_prep_f16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned short*)X_dev, B, HW, C, scale_dev, shift_dev, (unsigned short*)Ah_dev, (unsigned short*)Al_dev);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_warp_affine_faces_f32(const uint8_t* images_dev, const int64_t* offsets_dev, const int32_t* hw_dev, const int32_t* face_image_dev,
@@ -1081,7 +1013,7 @@ int mq_warp_affine_faces_f32(const uint8_t* images_dev, const int64_t* offsets_d
     const int total = nfaces * size * size;
     hipLaunchKernelGGL(warp_affine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images_dev,
                        (const long long*)offsets_dev, (const int*)hw_dev, (const int*)face_image_dev, minv_dev, nfaces, size, out_dev);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 }  // extern "C"

@@ -9,10 +9,11 @@
 #include <cstdint>
 
 #include "../../include/meerqat_hip.h"
+#include "device_common.h"
+#include "host_check.h"
 
 namespace {
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
+using namespace mq_dev;
 
 __device__ __forceinline__ unsigned mix(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(1024) void mfma_loop_kernel(int iters, int random_o
         a[i] = operand(tid * 8u + i, random_operands);
         b[i] = operand(tid * 8u + 4 + i, random_operands);
     }
-    f32x16_t c0 = {0}, c1 = {0}, c2 = {0}, c3 = {0};
+    f32x16 c0 = {0}, c1 = {0}, c2 = {0}, c3 = {0};
     for (int it = 0; it < iters; ++it) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {  // 16 MFMAs: the 2 x 2 sub-tile pattern of the scans
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(1024) void mfma_loop_kernel(int iters, int random_o
 __global__ __launch_bounds__(64) void mfma_dot_kernel(const unsigned short* __restrict__ A, const unsigned short* __restrict__ B, int dp,
                                                       float* __restrict__ out) {
     const int lane = threadIdx.x, i = lane & 31, kg = lane >> 5;
-    f32x16_t c = {0};
+    f32x16 c = {0};
     for (int k0 = 0; k0 < dp; k0 += 16) {
         const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(A + (size_t)i * dp + k0 + 8 * kg);
         const bf16x8_t b = *reinterpret_cast<const bf16x8_t*>(B + (size_t)i * dp + k0 + 8 * kg);
@@ -75,12 +76,12 @@ extern "C" {
 int mq_diag_mfma_bf16_dot(const uint16_t* A_dev, const uint16_t* B_dev, int dp, float* out_dev, void* stream) {
     if (!A_dev || !B_dev || !out_dev || dp <= 0 || dp % 16 != 0) return MQ_EINVAL;
     hipLaunchKernelGGL(mfma_dot_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, A_dev, B_dev, dp, out_dev);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_diag_mfma_bf16_loop(int iters, int random_operands, int workgroups, float* out_dev, void* stream) {
     if (iters < 0 || workgroups <= 0 || !out_dev) return MQ_EINVAL;
     hipLaunchKernelGGL(mfma_loop_kernel, dim3((unsigned)workgroups), dim3(1024), 0, (hipStream_t)stream, iters, random_operands, out_dev);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 }

@@ -21,30 +21,12 @@
 #include <mutex>
 
 #include "../../include/meerqat_hip.h"
-#include "launch_attr.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "device_common.h"
+#include "host_check.h"
 
 namespace {
 
-#define ENC_HIP(call)                                  \
-    do {                                               \
-        hipError_t _e = (call);                        \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
-
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(unsigned long)(lds_char*)p; }
-// one 1-KiB LDS-DMA piece: LDS destination = lds_dst (wave-uniform) + lane*16, global source per lane.
-// Issued from inline asm so hipcc does not drain it in front of the next ds_read (see knn.hip).
-// wave-uniform 64-bit base (SGPR pair) + per-lane 32-bit byte offset: the per-step update is scalar
-__device__ __forceinline__ void dma16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
+using namespace mq_dev;
 
 // ------------------------------------------------------------------------------------------------
 // GEMM  C = A . W^T
@@ -213,45 +195,18 @@ __global__ __launch_bounds__(1024) void gemm_nt_kernel(const float* __restrict__
 // Tile 256x256, BK 32, 2-stage LDS: per stage A fp32 [256][32] (128-B rows, chunks swizzled by (r>>1)&7)
 // + Wh, Wl bf16 [256][32] (64-B rows, chunks swizzled by (r>>2)&3) = 64 KiB.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 constexpr int XBK = 32;
 constexpr int X_A_BYTES = GT * XBK * 4;   // 32 KiB
 constexpr int X_W_BYTES = GT * XBK * 2;   // 16 KiB
 constexpr int X_STAGE = X_A_BYTES + 2 * X_W_BYTES;
 constexpr int X_LDS_BYTES = 2 * X_STAGE;  // 128 KiB
 
-__device__ __forceinline__ void split8(const float4& u, const float4& v, bf16x8_t& hi, bf16x8_t& lo) {
-    const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h = (__bf16)x[e];
-        hi[e] = h;
-        lo[e] = (__bf16)(x[e] - (float)h);
-    }
-}
-
-// four values -> their packed (hi, lo) bf16 quadruples (8 bytes each), the arithmetic of split8()
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split4(const float x0, const float x1, const float x2, const float x3, uint2& hi, uint2& lo) {
-    const float x[4] = {x0, x1, x2, x3};
-    bf16x4_t h4, l4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const __bf16 h = (__bf16)x[e];
-        h4[e] = h;
-        l4[e] = (__bf16)(x[e] - (float)h);
-    }
-    hi = __builtin_bit_cast(uint2, h4);
-    lo = __builtin_bit_cast(uint2, l4);
-}
-
 __global__ void split_bf16_kernel(const float* __restrict__ src, long long n, unsigned short* __restrict__ hi,
                                   unsigned short* __restrict__ lo) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    const float x = src[e];
-    const __bf16 h = (__bf16)x;
-    const __bf16 l = (__bf16)(x - (float)h);
+    __bf16 h, l;
+    split1(src[e], h, l);
     hi[e] = __builtin_bit_cast(unsigned short, h);
     lo[e] = __builtin_bit_cast(unsigned short, l);
 }
@@ -271,9 +226,8 @@ __global__ void split_bf16_tiled_kernel(const float* __restrict__ src, int N, in
     if (n < N) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float x = src[n * K + k + j];
-            const __bf16 hb = (__bf16)x;
-            const __bf16 lb = (__bf16)(x - (float)hb);
+            __bf16 hb, lb;
+            split1(src[n * K + k + j], hb, lb);
             h[j] = __builtin_bit_cast(unsigned short, hb);
             l[j] = __builtin_bit_cast(unsigned short, lb);
         }
@@ -286,31 +240,7 @@ __global__ void split_bf16_tiled_kernel(const float* __restrict__ src, int N, in
 // Split activations.  An activation tensor that only feeds GEMMs is kept as its (hi, lo) bf16 pair, written by the
 // kernel that PRODUCES it (LayerNorm, attention, the GELU epilogue): the consuming GEMM then streams bf16 operands
 // only and carries no conversions in its MFMA loop (measured: the in-loop split cost 18-22 % of encoder time).
-// hi = bf16(x), lo = bf16(x - hi): exactly what split8() computes, so both GEMM variants give identical results.
-// store_split_pair: lanes l and l^1 of a wave hold ADJACENT columns (even column in the even lane); after one DPP
-// exchange the even lane stores the packed hi pair, the odd lane the packed lo pair -- one 4-byte store per lane.
-__device__ __forceinline__ unsigned split_bits(float x) {
-    const __bf16 h = (__bf16)x;
-    const __bf16 l = (__bf16)(x - (float)h);
-    return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
-}
-// PAIR LAYOUT.  The (hi, lo) arrays of a split activation [M, K] (K a multiple of 32) are stored tile by tile, exactly like the
-// weights of split_bf16_tiled_kernel: element (row, col) lives at pair_index(row, col, K) = [row / 256][col / 32][row % 256][col % 32],
-// and the arrays hold ceil(M / 256) * 256 * K elements (rows beyond M are never written, and never read: the GEMM's A stream
-// re-reads row M - 1 instead).  The A operand of one K step of a GEMM tile is then one contiguous 16-KiB block; 8 consecutive
-// columns of a row (what the producers store at once) stay 16 contiguous bytes.
-__device__ __forceinline__ size_t pair_index(size_t row, int col, int K) {
-    return ((row >> 8) * (size_t)(K >> 5) + (size_t)(col >> 5)) * (GT * XBK) + ((row & 255) << 5) + (size_t)(col & 31);
-}
-__device__ __forceinline__ void store_split_pair(float x, bool valid, unsigned short* __restrict__ hi, unsigned short* __restrict__ lo,
-                                                 size_t even_col_index, int lane) {
-    const unsigned mine = split_bits(x);
-    const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)mine, 0xB1, 0xF, 0xF, false);  // lane ^ 1
-    const bool odd = lane & 1;
-    const unsigned ev = odd ? other : mine, od = odd ? mine : other;  // the pair's even / odd column
-    const unsigned word = odd ? ((ev >> 16) | (od & 0xFFFF0000u)) : ((ev & 0xFFFFu) | (od << 16));
-    if (valid) *reinterpret_cast<unsigned*>((odd ? lo : hi) + even_col_index) = word;
-}
+// hi = bf16(x), lo = bf16(x - hi) in the PAIR LAYOUT (device_common.h), so both GEMM variants give identical results.
 
 #ifndef MQ_GEMM_F32_VIA_LDS
 // fp32 outputs of whole tiles leave through the LDS transposition (16-byte stores) like the split ones, unless a residual is added:
@@ -522,6 +452,7 @@ __global__ __launch_bounds__(1024) void gemm_nt_x3s_kernel(const unsigned short*
         // (one column per lane), the residual after the transposition: per element the operations and their order are those
         // of the direct epilogue, so the results keep their bits.  Scratch: the LDS stage the K loop has just finished with
         // (the other one may be receiving the next tile's first K step), 4 KiB per wave, 16-byte groups XOR-swizzled by the row.
+        // The same walk stands in conv.hip and resnet.hip: shared as one function with functors it changes the kernels' assembly.
         __syncthreads();  // every wave has read its last operands from that stage
         float* Ot = reinterpret_cast<float*>(smem + (stage ^ 1) * XS_STAGE) + w * 1024;
         const int nb0 = n0 + 64 * wc + i, nb1 = nb0 + 32;
@@ -732,12 +663,6 @@ __global__ __launch_bounds__(1024) void gemm_nt_x3_kernel(const float* __restric
 // LayerNorm family: one wave per row, row held in registers (C <= 1024)
 // ------------------------------------------------------------------------------------------------
 constexpr int LN_MAXPER = 16;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // normalises v[] (this lane's elements c = lane + 64 t, t < nper) and stores
 // out (fp32 row, may be null) and/or oh, ol (the row's split pair, may be null; C even then)
@@ -1429,7 +1354,7 @@ int mq_gemm_nt_f32(const float* A_dev, const float* W_dev, const float* bias_dev
     hipStream_t st = (hipStream_t)stream;
 #define MQ_LAUNCH(E)                                                                                                  \
     case E:                                                                                                           \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, G_LDS_BYTES, gemm_nt_kernel<E>); \
+        MQ_DYNAMIC_LDS(G_LDS_BYTES, gemm_nt_kernel<E>); \
         hipLaunchKernelGGL(gemm_nt_kernel<E>, grid, block, G_LDS_BYTES, st, A_dev, W_dev, bias_dev, residual_dev, C_dev, M, N, K, ntm, ntn); \
         break;
     switch (epilogue) {
@@ -1440,8 +1365,7 @@ int mq_gemm_nt_f32(const float* A_dev, const float* W_dev, const float* bias_dev
         MQ_LAUNCH(EPI_BIAS_RESIDUAL)
     }
 #undef MQ_LAUNCH
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_split_bf16_f32(const float* src_dev, int64_t n, uint16_t* hi_dev, uint16_t* lo_dev, void* stream) {
@@ -1449,8 +1373,7 @@ int mq_split_bf16_f32(const float* src_dev, int64_t n, uint16_t* hi_dev, uint16_
     if (!src_dev || !hi_dev || !lo_dev || n < 0) return MQ_EINVAL;
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src_dev, (long long)n,
                        (unsigned short*)hi_dev, (unsigned short*)lo_dev);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int64_t mq_split_bf16_tiled_elems(int N, int K) { return (int64_t)((N + GT - 1) / GT) * GT * (int64_t)K; }
@@ -1462,8 +1385,7 @@ int mq_split_bf16_tiled_f32(const float* W_dev, int N, int K, uint16_t* hi_dev, 
     const long long quads = (long long)mq_split_bf16_tiled_elems(N, K) / 4;
     hipLaunchKernelGGL(split_bf16_tiled_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W_dev, N, K,
                        (unsigned short*)hi_dev, (unsigned short*)lo_dev);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_gemm_nt_bf16x3_f32(const float* A_dev, const uint16_t* Wh_dev, const uint16_t* Wl_dev, const float* bias_dev,
@@ -1481,7 +1403,7 @@ int mq_gemm_nt_bf16x3_f32(const float* A_dev, const uint16_t* Wh_dev, const uint
     hipStream_t st = (hipStream_t)stream;
 #define MQ_LAUNCH(E)                                                                                                  \
     case E:                                                                                                           \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, X_LDS_BYTES, gemm_nt_x3_kernel<E>); \
+        MQ_DYNAMIC_LDS(X_LDS_BYTES, gemm_nt_x3_kernel<E>); \
         hipLaunchKernelGGL(gemm_nt_x3_kernel<E>, grid, block, X_LDS_BYTES, st, A_dev, (const unsigned short*)Wh_dev,    \
                            (const unsigned short*)Wl_dev, bias_dev, residual_dev, C_dev, M, N, K, ntm, ntn, wt);       \
         break;
@@ -1493,8 +1415,7 @@ int mq_gemm_nt_bf16x3_f32(const float* A_dev, const uint16_t* Wh_dev, const uint
         MQ_LAUNCH(EPI_BIAS_RESIDUAL)
     }
 #undef MQ_LAUNCH
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 static int gemm_x3s_launch(const uint16_t* Ah_dev, const uint16_t* Al_dev, const uint16_t* Wh_dev, const uint16_t* Wl_dev,
@@ -1521,7 +1442,7 @@ static int gemm_x3s_launch(const uint16_t* Ah_dev, const uint16_t* Al_dev, const
     const dim3 block_w(512);
 #define MQ_LAUNCHW(E, S, P)                                                                                            \
     {                                                                                                                 \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, XW_LDS_BYTES, gemm_nt_x3w_kernel<E, S, P>); \
+        MQ_DYNAMIC_LDS(XW_LDS_BYTES, gemm_nt_x3w_kernel<E, S, P>); \
         hipLaunchKernelGGL((gemm_nt_x3w_kernel<E, S, P>), grid, block_w, XW_LDS_BYTES, st, (const unsigned short*)Ah_dev,  \
                            (const unsigned short*)Al_dev, (const unsigned short*)Wh_dev, (const unsigned short*)Wl_dev, \
                            bias_dev, residual_dev, C_dev, (unsigned short*)Ch_dev, (unsigned short*)Cl_dev, M, N, K, ntm, ntn, wt, nsplit, \
@@ -1533,7 +1454,7 @@ static int gemm_x3s_launch(const uint16_t* Ah_dev, const uint16_t* Al_dev, const
     } else if (wide) {                                                                                                \
         MQ_LAUNCHW(E, S, false)                                                                                        \
     } else {                                                                                                          \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, XS_LDS_BYTES, gemm_nt_x3s_kernel<E, S>); \
+        MQ_DYNAMIC_LDS(XS_LDS_BYTES, gemm_nt_x3s_kernel<E, S>); \
         hipLaunchKernelGGL((gemm_nt_x3s_kernel<E, S>), grid, block, XS_LDS_BYTES, st, (const unsigned short*)Ah_dev,    \
                            (const unsigned short*)Al_dev, (const unsigned short*)Wh_dev, (const unsigned short*)Wl_dev, \
                            bias_dev, residual_dev, C_dev, (unsigned short*)Ch_dev, (unsigned short*)Cl_dev, M, N, K, ntm, ntn, wt, nsplit, \
@@ -1553,8 +1474,7 @@ static int gemm_x3s_launch(const uint16_t* Ah_dev, const uint16_t* Al_dev, const
 #undef MQ_LAUNCH
 #undef MQ_LAUNCH2
 #undef MQ_LAUNCHW
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_gemm_set_option(int which, int value) {
@@ -1593,8 +1513,7 @@ int mq_gemm_nt_bf16x3s_splitk_f32(const uint16_t* Ah_dev, const uint16_t* Al_dev
     const size_t mn = (size_t)M * N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, (hipStream_t)stream, partials_dev, bias_dev,
                        C_dev, nsplit, mn, N);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_layernorm_f32(const float* X_dev, const float* gamma_dev, const float* beta_dev, float* Y_dev, int M, int C, float eps,
@@ -1616,8 +1535,7 @@ int mq_layernorm_split_f32(const float* X_dev, const float* gamma_dev, const flo
     else
         hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, X_dev, gamma_dev,
                            beta_dev, Y_dev, (unsigned short*)Yh_dev, (unsigned short*)Yl_dev, M, C, eps);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_bert_embed_ln_f32(const int64_t* input_ids_dev, const int64_t* token_type_ids_dev, const float* word_dev,
@@ -1640,8 +1558,7 @@ int mq_bert_embed_ln_split_f32(const int64_t* input_ids_dev, const int64_t* toke
     hipLaunchKernelGGL(bert_embed_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)input_ids_dev, (const long long*)token_type_ids_dev, word_dev, pos_dev, type_dev,
                        gamma_dev, beta_dev, out_dev, (unsigned short*)out_h_dev, (unsigned short*)out_l_dev, M, L, H, eps);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_bert_embed_ln_packed_f32(const int64_t* input_ids_dev, const int64_t* token_type_ids_dev, const int32_t* position_ids_dev,
@@ -1658,8 +1575,7 @@ int mq_bert_embed_ln_packed_f32(const int64_t* input_ids_dev, const int64_t* tok
                        (const long long*)input_ids_dev, (const long long*)token_type_ids_dev, word_dev, pos_dev, type_dev,
                        gamma_dev, beta_dev, out_dev, (unsigned short*)out_h_dev, (unsigned short*)out_l_dev, T, 1, H, eps,
                        (const int*)position_ids_dev);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_attention_f32(const float* qkv_dev, const int64_t* attention_mask_dev, float* out_dev, int B, int L, int heads,
@@ -1686,7 +1602,7 @@ int mq_attention_split_f32(const float* qkv_dev, const int64_t* attention_mask_d
 #define MQ_ATT(NKT, MULTI)                                                                                                   \
     {                                                                                                                 \
         const size_t lds = (size_t)(32 * NKT) * (65 + 64 + 1) * 4 > (size_t)4 * 32 * 65 * 4 ? (size_t)(32 * NKT) * (65 + 64 + 1) * 4 : (size_t)4 * 32 * 65 * 4; \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, mq_detail::LDS_PER_CU, attention_mfma_kernel<NKT, MULTI>); \
+        MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, attention_mfma_kernel<NKT, MULTI>); \
         hipLaunchKernelGGL((attention_mfma_kernel<NKT, MULTI>), grid, dim3(nthr), lds, st, qkv_dev, (const long long*)attention_mask_dev,    \
                            out_dev, (unsigned short*)out_h_dev, (unsigned short*)out_l_dev, L, heads, scale, causal ? 1 : 0); \
     }
@@ -1694,7 +1610,7 @@ int mq_attention_split_f32(const float* qkv_dev, const int64_t* attention_mask_d
     {                                                                                                                 \
         const size_t need = (size_t)(32 * NKT) * 128 * 2 + (size_t)64 * (32 * NKT) * 2 * 2 + (size_t)(32 * NKT) * 4;    \
         const size_t lds = need > (size_t)4 * 32 * 65 * 4 ? need : (size_t)4 * 32 * 65 * 4;                           \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, mq_detail::LDS_PER_CU, attention_x3_kernel<NKT, MULTI>); \
+        MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, attention_x3_kernel<NKT, MULTI>); \
         hipLaunchKernelGGL((attention_x3_kernel<NKT, MULTI>), grid, dim3(nthr), lds, st, qkv_dev, (const long long*)attention_mask_dev,    \
                            out_dev, (unsigned short*)out_h_dev, (unsigned short*)out_l_dev, L, heads, scale, causal ? 1 : 0); \
     }
@@ -1712,8 +1628,7 @@ int mq_attention_split_f32(const float* qkv_dev, const int64_t* attention_mask_d
     }
 #undef MQ_ATT
 #undef MQ_ATT3
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_attention_packed_f32(const float* qkv_dev, const int32_t* cu_seqlens_dev, const int32_t* seq_ids_dev, int n_seqs,
@@ -1731,7 +1646,7 @@ int mq_attention_packed_f32(const float* qkv_dev, const int32_t* cu_seqlens_dev,
 #define MQ_ATTP(NKT, MULTI)                                                                                                  \
     {                                                                                                                 \
         const size_t lds = (size_t)(32 * NKT) * (65 + 64 + 1) * 4 > (size_t)4 * 32 * 65 * 4 ? (size_t)(32 * NKT) * (65 + 64 + 1) * 4 : (size_t)4 * 32 * 65 * 4; \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, mq_detail::LDS_PER_CU, attention_mfma_kernel<NKT, MULTI>); \
+        MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, attention_mfma_kernel<NKT, MULTI>); \
         hipLaunchKernelGGL((attention_mfma_kernel<NKT, MULTI>), grid, dim3(nthr), lds, st, qkv_dev, (const long long*)nullptr,    \
                            out_dev, (unsigned short*)out_h_dev, (unsigned short*)out_l_dev, L, heads, scale, causal ? 1 : 0, \
                            (const int*)cu_seqlens_dev, (const int*)seq_ids_dev); \
@@ -1740,7 +1655,7 @@ int mq_attention_packed_f32(const float* qkv_dev, const int32_t* cu_seqlens_dev,
     {                                                                                                                 \
         const size_t need = (size_t)(32 * NKT) * 128 * 2 + (size_t)64 * (32 * NKT) * 2 * 2 + (size_t)(32 * NKT) * 4;    \
         const size_t lds = need > (size_t)4 * 32 * 65 * 4 ? need : (size_t)4 * 32 * 65 * 4;                           \
-        MQ_DYNAMIC_LDS_WITH(ENC_HIP, mq_detail::LDS_PER_CU, attention_x3_kernel<NKT, MULTI>); \
+        MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, attention_x3_kernel<NKT, MULTI>); \
         hipLaunchKernelGGL((attention_x3_kernel<NKT, MULTI>), grid, dim3(nthr), lds, st, qkv_dev, (const long long*)nullptr,    \
                            out_dev, (unsigned short*)out_h_dev, (unsigned short*)out_l_dev, L, heads, scale, causal ? 1 : 0, \
                            (const int*)cu_seqlens_dev, (const int*)seq_ids_dev); \
@@ -1754,7 +1669,7 @@ int mq_attention_packed_f32(const float* qkv_dev, const int32_t* cu_seqlens_dev,
             const size_t need = (size_t)256 * 128 * 2 + (size_t)64 * 256 * 2 * 2 + (size_t)256 * 4;
             const size_t ot = (size_t)8 * 32 * 65 * 4;
             const size_t lds = need > ot ? need : ot;
-            MQ_DYNAMIC_LDS_WITH(ENC_HIP, mq_detail::LDS_PER_CU, attention_x3_kernel<8, false, true>);
+            MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, attention_x3_kernel<8, false, true>);
             hipLaunchKernelGGL((attention_x3_kernel<8, false, true>), dim3((unsigned)(n_seqs * heads), 1u), dim3(64u * (unsigned)((L + 31) / 32)),
                                lds, st, qkv_dev, (const long long*)nullptr, out_dev, (unsigned short*)out_h_dev,
                                (unsigned short*)out_l_dev, L, heads, scale, causal ? 1 : 0, (const int*)cu_seqlens_dev,
@@ -1769,8 +1684,7 @@ int mq_attention_packed_f32(const float* qkv_dev, const int32_t* cu_seqlens_dev,
     }
 #undef MQ_ATTP
 #undef MQ_ATTP3
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_sum_groups_f32(const float* x_dev, const float* init_dev, float* out_dev, int G, int n, int H, void* stream) {
@@ -1779,8 +1693,7 @@ int mq_sum_groups_f32(const float* x_dev, const float* init_dev, float* out_dev,
     const size_t total = (size_t)G * H;
     hipLaunchKernelGGL(sum_groups_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, init_dev,
                        out_dev, G, n, H);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_clip_text_embed_f32(const int64_t* input_ids_dev, const float* token_emb_dev, const float* pos_emb_dev, float* out_dev,
@@ -1790,8 +1703,7 @@ int mq_clip_text_embed_f32(const int64_t* input_ids_dev, const float* token_emb_
     const int M = B * L;
     hipLaunchKernelGGL(clip_text_embed_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)input_ids_dev, token_emb_dev, pos_emb_dev, out_dev, M, L, H, (const int*)nullptr);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_clip_text_embed_packed_f32(const int64_t* input_ids_dev, const int32_t* position_ids_dev, const float* token_emb_dev,
@@ -1801,8 +1713,7 @@ int mq_clip_text_embed_packed_f32(const int64_t* input_ids_dev, const int32_t* p
     hipLaunchKernelGGL(clip_text_embed_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)input_ids_dev, token_emb_dev, pos_emb_dev, out_dev, T, 1, H,
                        (const int*)position_ids_dev);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_clip_eos_pool_ln_f32(const float* hidden_dev, const int64_t* input_ids_dev, int64_t eos_token_id, const float* gamma_dev,
@@ -1812,8 +1723,7 @@ int mq_clip_eos_pool_ln_f32(const float* hidden_dev, const int64_t* input_ids_de
     if (H > 64 * LN_MAXPER) return MQ_EUNSUPPORTED;
     hipLaunchKernelGGL(clip_eos_pool_ln_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, hidden_dev,
                        (const long long*)input_ids_dev, (long long)eos_token_id, gamma_dev, beta_dev, out_dev, B, L, H, eps);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_clip_patchify_f32(const float* pixels_dev, float* patches_dev, int B, int channels, int image_size, int patch_size,
@@ -1824,8 +1734,7 @@ int mq_clip_patchify_f32(const float* pixels_dev, float* patches_dev, int B, int
     const size_t total4 = (size_t)B * channels * image_size * image_size / 4;
     hipLaunchKernelGGL(clip_patchify_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pixels_dev,
                        patches_dev, B, channels, image_size, patch_size);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_clip_assemble_ln_f32(const float* patch_emb_dev, const float* class_emb_dev, const float* pos_emb_dev,
@@ -1838,8 +1747,7 @@ int mq_clip_assemble_ln_f32(const float* patch_emb_dev, const float* class_emb_d
     const int M = B * tokens;
     hipLaunchKernelGGL(clip_assemble_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, patch_emb_dev,
                        class_emb_dev, pos_emb_dev, gamma_dev, beta_dev, out_dev, M, tokens, H, eps);
-    ENC_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 }  // extern "C"

@@ -24,17 +24,12 @@
 #include <math.h>
 
 #include "../../include/meerqat_hip.h"
-#include "launch_attr.h"
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "device_common.h"
+#include "host_check.h"
 
 namespace {
 
-#define FUSE_HIP(call)                                 \
-    do {                                               \
-        hipError_t _e = (call);                        \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
+using namespace mq_dev;
 
 constexpr int FT = 256;          // threads per query workgroup
 constexpr int FCAP = 4096;       // most entries (R*K, rounded up to a power of two) one query may hold
@@ -54,15 +49,6 @@ struct FuseArgs {
     int R, nq, K, nsort, norm, defmin;
     double w[MQ_FUSE_MAX_RUNS];
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
 
 // ascending bitonic sort of nsort (a, b) pairs held in LDS, lexicographic on (a, b)
 __device__ void bitonic_pairs(uint64_t* a, uint64_t* b, int nsort) {
@@ -517,17 +503,16 @@ extern "C" int mq_fuse_wsum_f64(const int64_t* ids_dev, const double* scores_dev
     A.R = n_runs; A.nq = nq; A.K = K; A.nsort = next_pow2(n_runs * K); A.norm = norm; A.defmin = defmin ? 1 : 0;
     for (int r = 0; r < MQ_FUSE_MAX_RUNS; ++r) A.w[r] = r < n_runs ? weights_host[r] : 0.0;
     const size_t lds = (size_t)A.nsort * 2 * sizeof(uint64_t);
-    MQ_DYNAMIC_LDS_WITH(FUSE_HIP, mq_detail::LDS_PER_CU, fuse_stats_kernel);
-    MQ_DYNAMIC_LDS_WITH(FUSE_HIP, mq_detail::LDS_PER_CU, fuse_combine_kernel);
+    MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, fuse_stats_kernel);
+    MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, fuse_combine_kernel);
     hipLaunchKernelGGL(fuse_stats_kernel, dim3(nq), dim3(FT), lds, st, A);
-    FUSE_HIP(hipGetLastError());
+    MQ_HIP(hipGetLastError());
     if (norm == MQ_FUSE_NORM_GZMUV) {
         hipLaunchKernelGGL(fuse_moments_kernel, dim3(n_runs), dim3(1024), 0, st, A);
-        FUSE_HIP(hipGetLastError());
+        MQ_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(fuse_combine_kernel, dim3(nq), dim3(FT), lds, st, A);
-    FUSE_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 extern "C" int mq_run_metrics_f64(const int64_t* ids_dev, int nq, int K, const int64_t* rel_ptr_dev,
@@ -544,10 +529,9 @@ extern "C" int mq_run_metrics_f64(const int64_t* ids_dev, int nq, int K, const i
     }
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(run_metrics_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, A);
-    FUSE_HIP(hipGetLastError());
+    MQ_HIP(hipGetLastError());
     hipLaunchKernelGGL(np_mean_rows_kernel, dim3((n_metrics + 63) / 64), dim3(64), 0, st, per_query_dev, mean_dev, n_metrics, nq);
-    FUSE_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 extern "C" int mq_fuse_fit_wsum_f64(const int64_t* ids_dev, const double* scores_dev, int n_runs, int nq, int K,
@@ -574,17 +558,16 @@ extern "C" int mq_fuse_fit_wsum_f64(const int64_t* ids_dev, const double* scores
     G.T = n_trials; G.code = metric; G.k = metric_k;
     const size_t lds = (size_t)A.nsort * 2 * sizeof(uint64_t);
     const size_t lds_fit = (size_t)A.nsort * (3 * sizeof(uint64_t) + 2 * sizeof(int));
-    MQ_DYNAMIC_LDS_WITH(FUSE_HIP, mq_detail::LDS_PER_CU, fuse_stats_kernel);
-    MQ_DYNAMIC_LDS_WITH(FUSE_HIP, mq_detail::LDS_PER_CU, fuse_fit_kernel);
+    MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, fuse_stats_kernel);
+    MQ_DYNAMIC_LDS(mq_detail::LDS_PER_CU, fuse_fit_kernel);
     hipLaunchKernelGGL(fuse_stats_kernel, dim3(nq), dim3(FT), lds, st, A);
-    FUSE_HIP(hipGetLastError());
+    MQ_HIP(hipGetLastError());
     if (norm == MQ_FUSE_NORM_GZMUV) {
         hipLaunchKernelGGL(fuse_moments_kernel, dim3(n_runs), dim3(1024), 0, st, A);
-        FUSE_HIP(hipGetLastError());
+        MQ_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(fuse_fit_kernel, dim3(nq), dim3(FT), lds_fit, st, G);
-    FUSE_HIP(hipGetLastError());
+    MQ_HIP(hipGetLastError());
     hipLaunchKernelGGL(np_mean_rows_kernel, dim3((n_trials + 63) / 64), dim3(64), 0, st, per_query_dev, mean_dev, n_trials, nq);
-    FUSE_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }

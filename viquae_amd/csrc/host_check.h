@@ -1,7 +1,28 @@
-// Shared by the .hip translation units of libmeerqat_hip.so.
+// The host side that the .hip translation units of libmeerqat_hip.so share: ONE way for a failing HIP call to become MQ_EHIP with
+// the error recorded for mq_last_hip_error(), and the dynamic-LDS attribute of a kernel raised once per device.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+
+#include "../../include/meerqat_hip.h"
+
+extern "C" void mq_internal_set_hip_error(int e);  // knn.hip: the calling thread's mq_last_hip_error()
+
+// in a function that returns an MQ_* status: on failure record the error and return MQ_EHIP
+#define MQ_HIP(call)                               \
+    do {                                           \
+        hipError_t _e = (call);                    \
+        if (_e != hipSuccess) {                    \
+            mq_internal_set_hip_error((int)_e);    \
+            return MQ_EHIP;                        \
+        }                                          \
+    } while (0)
+
+// the status of the kernel launch(es) just made
+inline int mq_launch_status() {
+    MQ_HIP(hipGetLastError());
+    return MQ_OK;
+}
 
 namespace mq_detail {
 
@@ -28,9 +49,9 @@ inline hipError_t ensure_dynamic_lds(const void* fn, int bytes, std::atomic<unsi
 
 }  // namespace mq_detail
 
-// CHECK = the translation unit's "return MQ_EHIP on failure" macro; the kernel expression may hold commas.
-#define MQ_DYNAMIC_LDS_WITH(CHECK, bytes, ...)                                                         \
+// the kernel expression may hold commas
+#define MQ_DYNAMIC_LDS(bytes, ...)                                                                      \
     do {                                                                                               \
         static std::atomic<unsigned long long> _mq_lds_done{0};                                        \
-        CHECK(mq_detail::ensure_dynamic_lds((const void*)(__VA_ARGS__), (int)(bytes), _mq_lds_done));  \
+        MQ_HIP(mq_detail::ensure_dynamic_lds((const void*)(__VA_ARGS__), (int)(bytes), _mq_lds_done)); \
     } while (0)

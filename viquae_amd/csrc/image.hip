@@ -22,16 +22,9 @@
 #include <math.h>
 
 #include "../../include/meerqat_hip.h"
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "host_check.h"
 
 namespace {
-
-#define IMG_HIP(call)                                  \
-    do {                                               \
-        hipError_t _e = (call);                        \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;  // Resample.c
 constexpr int G = MQ_IMAGE_GEOM;            // int64 fields per image, see mq_image_plan
@@ -388,8 +381,7 @@ int mq_image_preprocess_u8(const uint8_t* src_dev, const int64_t* geom_dev, int 
                        (size_t)a.rpb * pitch + tile_bytes, st, a);
     hipLaunchKernelGGL(resample_cols_kernel, dim3((crop_h + COLS_ROWS - 1) / COLS_ROWS, n_images), dim3(256),
                        (size_t)COLS_ROWS * align_up((size_t)crop_w * 3 + 4, 16), st, a);
-    IMG_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 }  // extern "C"

@@ -26,16 +26,9 @@
 #include <string.h>
 
 #include "../../include/meerqat_hip.h"
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "host_check.h"
 
 namespace {
-
-#define JPG_HIP(call)                                  \
-    do {                                               \
-        hipError_t _e = (call);                        \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
 
 // header words (int32) in front of an image's coefficient blocks; the quantisation tables follow at byte 128
 enum { H_MAGIC = 0, H_HEIGHT, H_WIDTH, H_NCOMP, H_HMAX, H_VMAX, H_MCUX, H_MCUY, H_CH = 8, H_CV = 11, H_BW = 14, H_BH = 17,
@@ -946,6 +939,5 @@ extern "C" int mq_jpeg_decode_rgb_u8(uint8_t* buf_dev, const int64_t* items_dev,
     if (max_blocks > 0)
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n_images), dim3(128), 0, st, buf_dev, items_dev);
     hipLaunchKernelGGL(jpeg_rgb_kernel, dim3((unsigned)((max_strips + 255) / 256), (unsigned)n_images), dim3(256), 0, st, buf_dev, items_dev);
-    JPG_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }

@@ -26,10 +26,10 @@
 #include <mutex>
 
 #include "../../include/meerqat_hip.h"
-#include "launch_attr.h"
+#include "device_common.h"
+#include "host_check.h"
 
 typedef unsigned long long u64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Code placement of the MFMA loop moves kernel time by +-4.5 % between 4-byte phases (measured,
 // profiles/r01_notes.md); MQ_PAD_NOPS shifts it.  Re-tune with tools/tune_placement.sh after edits.
@@ -38,6 +38,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #endif
 
 namespace {
+
+using namespace mq_dev;
 
 // A/B switches of the search paths (mq_knn_set_option, include/meerqat_hip.h): process-wide atomics whose FIRST values come
 // from the environment (MQ_KNN_SMALL, MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS), read once.  Tests and bench.py flip them
@@ -92,33 +94,6 @@ __device__ __forceinline__ float key_score(u64 key) {
     unsigned b = (unsigned)(key >> 32);
     b = (b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b;
     return __uint_as_float(b);
-}
-typedef __attribute__((address_space(3))) char lds_char;
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(unsigned long)(lds_char*)p; }
-// one 1-KiB LDS-DMA piece: LDS destination = lds_dst (wave-uniform) + lane*16, source per lane
-__device__ __forceinline__ void dma16(const float* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// same piece with a wave-uniform 64-bit base (SGPR pair) + per-lane 32-bit byte offset: the per-step
-// address update is scalar arithmetic only
-__device__ __forceinline__ void dma16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// the same piece with the non-temporal cache policy (streamed-once operands; measured per kernel)
-__device__ __forceinline__ void dma16s_nt(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// a 4-byte-per-lane LDS-DMA piece (256 bytes per full wave; inactive lanes move nothing): LDS destination = lds_dst + lane * 4
-__device__ __forceinline__ void dma4s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
 __device__ __forceinline__ unsigned key_row(u64 key) { return 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull); }
 
@@ -623,8 +598,8 @@ __global__ __launch_bounds__(1024) void knn_scan_kernel(const ScanArgs a) {
     // with the builtin it drains vmcnt(0) in front of the next ds_read and the prefetch of step t+1
     // would serialise with the MFMAs of step t.  Completion is awaited by hand (vmcnt(0) right
     // before the barrier that opens the step which reads the data).
-    const unsigned lds_x = __builtin_amdgcn_readfirstlane(lds_addr(Xs + lds_piece));
-    const unsigned lds_q = __builtin_amdgcn_readfirstlane(lds_addr(Qs + lds_piece));
+    const unsigned lds_x = __builtin_amdgcn_readfirstlane(lds_addr_of(Xs + lds_piece));
+    const unsigned lds_q = __builtin_amdgcn_readfirstlane(lds_addr_of(Qs + lds_piece));
     auto issue = [&](int c, int kb, int stage) __attribute__((always_inline)) {
         const char* xb = xbase0 + (size_t)c * chunk_bytes + (size_t)kb * (BK * PANEL * 4);
         const char* qb = qbase0 + (size_t)kb * (BK * PANEL * 4);
@@ -1007,16 +982,6 @@ __global__ __launch_bounds__(256) void shard_merge_big_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------
 thread_local int g_last_hip_error = 0;
 
-inline int hip_fail(hipError_t e) {
-    g_last_hip_error = (int)e;
-    return MQ_EHIP;
-}
-#define MQ_HIP(call)                                   \
-    do {                                               \
-        hipError_t _e = (call);                        \
-        if (_e != hipSuccess) return hip_fail(_e);     \
-    } while (0)
-
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // Cycle-accounting builds (-DMQ_TIMING, tools/scan_timing.py) hand the kernels a device buffer for their
@@ -1030,8 +995,6 @@ inline unsigned long long* dbg_ptr() {
     return nullptr;
 #endif
 }
-
-#define MQ_DYNAMIC_LDS(bytes, ...) MQ_DYNAMIC_LDS_WITH(MQ_HIP, bytes, __VA_ARGS__)
 
 int num_cus() {
     static int cached = 0;  // idempotent, benign race
@@ -1211,7 +1174,7 @@ int mq_knn_get_option(int key) {
 }
 
 int mq_last_hip_error(void) { return g_last_hip_error; }
-void mq_internal_set_hip_error(int e) { g_last_hip_error = e; }  /* used by encoder.hip */
+void mq_internal_set_hip_error(int e) { g_last_hip_error = e; }  /* MQ_HIP, host_check.h */
 
 int64_t mq_padded_rows(int64_t n_rows) { return round_up(n_rows > 0 ? n_rows : 1, TN); }
 int mq_padded_dim(int d) { return (int)round_up(d, BK); }
@@ -1226,8 +1189,7 @@ int mq_pack_rows_f32(const float* rows_dev, int64_t n, int d, int64_t row_offset
     const unsigned grid = (unsigned)((n + PANEL - 1) / PANEL);
     hipLaunchKernelGGL(pack_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows_dev, n, d, dpad, row_offset,
                        l2norm, packed_dev, sqnorm_dev);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_unpack_rows_f32(const float* packed_dev, int64_t capacity_rows, int d, int64_t row_offset, int64_t n,
@@ -1239,16 +1201,14 @@ int mq_unpack_rows_f32(const float* packed_dev, int64_t capacity_rows, int d, in
     const unsigned grid = (unsigned)((total + 255) / 256);
     hipLaunchKernelGGL(unpack_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, packed_dev, d, dpad, row_offset, n,
                        rows_dev);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_l2norm_rows_form_f32(float* rows_dev, int64_t n, int d, int form, void* stream) {
     if (n == 0) return MQ_OK;
     if (!rows_dev || n < 0 || d <= 0 || (form != MQ_L2NORM_NUMPY && form != MQ_L2NORM_FAISS)) return MQ_EINVAL;
     launch_l2norm_rows(rows_dev, n, d, form, (hipStream_t)stream);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_l2norm_rows_f32(float* rows_dev, int64_t n, int d, void* stream) {
@@ -1448,8 +1408,7 @@ static int launch_scan_m(bool xrow, bool ceil, const ScanArgs& a, hipStream_t st
     else if (xrow && !ceil) { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, true, false>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, true, false>), grid, block, LDS_TOTAL, st, a); }
     else if (!xrow) { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, false, true>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, false, true>), grid, block, LDS_TOTAL, st, a); }
     else { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, true, true>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, true, true>), grid, block, LDS_TOTAL, st, a); }
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 static int launch_scan(int metric, bool xrow, bool ceil, const ScanArgs& a, hipStream_t st) {
     return metric == MQ_METRIC_L2 ? launch_scan_m<MQ_METRIC_L2>(xrow, ceil, a, st) : launch_scan_m<MQ_METRIC_IP>(xrow, ceil, a, st);
@@ -1464,8 +1423,7 @@ static int pack_query_panels(const Geometry& g, const float* q, int nq, int d, i
     const unsigned panels = clear ? (unsigned)((nq + PANEL - 1) / PANEL) : (unsigned)(g.nqpad / PANEL);
     hipLaunchKernelGGL(pack_rows_kernel, dim3(panels), dim3(256), 0, st, q, (int64_t)nq, d, g.dpad, (int64_t)0, form, Qp, qn, only,
                        clear ? (int64_t)0 : (int64_t)g.nqpad);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 // the exact scan's arguments over X (the panel copy, or the row-major copy) for the query panels Qp / qn
@@ -1486,8 +1444,7 @@ static int launch_slab_merge(int metric, const u64* lists, int nq, int S, int k,
     else
         hipLaunchKernelGGL(slab_merge_kernel<MQ_METRIC_L2>, dim3((unsigned)nq), dim3(128), 0, st, lists, nq, S, k, (long long)id_offset,
                            D_dev, (long long*)I_dev, only, flip, kout, col0, next_ceil);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 // The exact scan over a shard whose query panels (a.Qp, a.qn) are ready: one fused scan + slab merge per round of KF
@@ -1581,8 +1538,7 @@ static int screen_copy_and_stats(const float* sqnorm_dev, int d, int metric, int
     hipLaunchKernelGGL(row_err_stats_kernel, dim3((unsigned)((n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048)), dim3(256), 0, st, rm,
                        (const unsigned short*)bf16_dev, n, d, dp, (unsigned*)xstats_dev, center_dev, row_offset,
                        metric == MQ_METRIC_L2 ? 1 : 0);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_knn_screen_prepare(const float* packed_dev, const float* sqnorm_dev, int64_t capacity_rows, int d, int metric,
@@ -1835,10 +1791,10 @@ int mq_knn_screen_stats(int64_t N, int d, int nq, int k, const void* ws_dev, int
     out[5] = mm < 9e12f ? (int64_t)(mm * 1e6f) : INT64_MAX;  /* max margin in 1e-6 units (INT64_MAX: infinite) */
     out[6] = g.S;
     free(ovf); free(cc); free(pc); free(mg);
-    if (e1 != hipSuccess) return hip_fail(e1);
-    if (e2 != hipSuccess) return hip_fail(e2);
-    if (e3 != hipSuccess) return hip_fail(e3);
-    if (e4 != hipSuccess) return hip_fail(e4);
+    MQ_HIP(e1);
+    MQ_HIP(e2);
+    MQ_HIP(e3);
+    MQ_HIP(e4);
     return MQ_OK;
 }
 
@@ -1864,8 +1820,7 @@ static int topk_merge_impl(const float* Ds_dev, const int64_t* Is_dev, size_t d_
     else
         hipLaunchKernelGGL(shard_merge_kernel<MQ_METRIC_L2>, dim3((unsigned)nq), dim3(128), 0, st, Ds_dev,
                            (const long long*)Is_dev, d_stride, i_stride, nshards, nq, k, D_dev, (long long*)I_dev, desc);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_topk_merge_f32(const float* Ds_dev, const int64_t* Is_dev, int nshards, int nq, int k, int metric, float* D_dev,

@@ -39,7 +39,6 @@
 // q.x - ||x||^2/2 = q.xc - ||x||^2/2 + q.c, its two extra columns keep -||x||^2/2 of the STORED rows, and the terms of
 // its bound that carry ||x||^2 keep the uncentred maximum.
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 #define MQ_SMFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
@@ -529,8 +528,8 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
     const size_t chunk_bytes = (size_t)TN * a.dp * 2;  // = nkb tiles of S_OP_BYTES
     const char* const xbase0 = reinterpret_cast<const char*>(a.Xb);
     const char* const qbase0 = reinterpret_cast<const char*>(a.Qb) + (size_t)qt * chunk_bytes;
-    const unsigned lds_x = __builtin_amdgcn_readfirstlane(lds_addr(smem + S_LDS_X + 16 * w * 128));
-    const unsigned lds_q = __builtin_amdgcn_readfirstlane(lds_addr(smem + S_LDS_Q + 16 * w * 128));
+    const unsigned lds_x = __builtin_amdgcn_readfirstlane(lds_addr_of(smem + S_LDS_X + 16 * w * 128));
+    const unsigned lds_q = __builtin_amdgcn_readfirstlane(lds_addr_of(smem + S_LDS_Q + 16 * w * 128));
     auto issue = [&](int c, int kb, int stage) __attribute__((always_inline)) {
         const char* xb = xbase0 + (size_t)c * chunk_bytes + (size_t)kb * S_OP_BYTES;
         const char* qb = qbase0 + (size_t)kb * S_OP_BYTES;

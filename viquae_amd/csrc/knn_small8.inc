@@ -76,13 +76,6 @@ struct SmallArgs {
     int nkb_copy;       // K blocks of the stored bf16 copy per 256-row block (= the kernel's NKB, + 1 with the fp32 row term)
 };
 
-// dma16s with the sc1 policy: the aux pieces
-__device__ __forceinline__ void dma16s_sc1(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 sc1\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
 template <int N>
 __device__ __forceinline__ void sm_wait_vm() {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
@@ -168,12 +161,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // free); the swizzle is applied to the SOURCE chunk.
     const int r8 = lane >> 3, ch = lane & 7;
     const unsigned voff = (unsigned)((8 * wr + r8) * 128 + ((ch ^ (((8 * wr + r8) >> 1) & 7)) * 16));
-    const unsigned lds_ring = __builtin_amdgcn_readfirstlane(lds_addr(smem)) + (unsigned)(wr * 1024);
-    const unsigned lds_auxg = __builtin_amdgcn_readfirstlane(lds_addr(smem + L_AUXG));
-    const unsigned lds_auxs = __builtin_amdgcn_readfirstlane(lds_addr(smem + L_AUXS));
+    const unsigned lds_ring = __builtin_amdgcn_readfirstlane(lds_addr_of(smem)) + (unsigned)(wr * 1024);
+    const unsigned lds_auxg = __builtin_amdgcn_readfirstlane(lds_addr_of(smem + L_AUXG));
+    const unsigned lds_auxs = __builtin_amdgcn_readfirstlane(lds_addr_of(smem + L_AUXS));
     const char* const xbase0 = reinterpret_cast<const char*>(a.Xb);
     const size_t blk_bytes = (size_t)(ROWTERM ? sa.nkb_copy : NKB) * S_OP_BYTES;  // (the stored copy keeps its 13th K block: the tile kernel reads it)
-    const unsigned lds_row = __builtin_amdgcn_readfirstlane(lds_addr(smem + L_ROW));
+    const unsigned lds_row = __builtin_amdgcn_readfirstlane(lds_addr_of(smem + L_ROW));
     const void* const gthr_src = a.gthr + qt * TQ;
     const void* const smax_src = a.smax + (size_t)(qt * TQ + (slab < TQ ? slab : 0)) * a.ms;
     auto tile_of = [&](const int j) { return tl0 + (j < nt ? j : j - nt); };

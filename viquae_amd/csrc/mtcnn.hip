@@ -26,16 +26,9 @@
 #include <math.h>
 
 #include "../../include/meerqat_hip.h"
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "host_check.h"
 
 namespace {
-
-#define MT_HIP(call)                                                                  \
-    do {                                                                              \
-        hipError_t _e = (call);                                                       \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
 
 // ---- packed weights (floats): per layer weight, bias[, PReLU slope], in network order
 constexpr int P_W1 = 0, P_B1 = P_W1 + 270, P_A1 = P_B1 + 10, P_W2 = P_A1 + 10, P_B2 = P_W2 + 1440, P_A2 = P_B2 + 16,
@@ -576,16 +569,15 @@ int mq_mtcnn_resample_u8_f32(const uint8_t* images_dev, const int64_t* offsets_d
     if (by > 64) by = 64;
     resample_kernel<<<dim3((unsigned)n_jobs, (unsigned)by), 256, 0, (hipStream_t)stream>>>(images_dev, offsets_dev, hw_dev, n_images,
                                                                                            jobs_dev, out_dev, out_floats, overflow_dev);
-    MT_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_mtcnn_pnet_f32(const float* in_dev, int64_t in_floats, const int64_t* levels_dev, const float* level_scale_dev, int n_levels,
                       int max_tiles, const float* weights_dev, float threshold, int n_images, int cap, float* rec_dev, int32_t* idx_dev,
                       int32_t* sub_dev, int32_t* count_dev, int32_t* overflow_dev, float* maps_dev, int64_t maps_floats, void* stream) {
     if (!count_dev || !overflow_dev || n_images <= 0 || n_levels < 0) return MQ_EINVAL;
-    MT_HIP(hipMemsetAsync(count_dev, 0, sizeof(int32_t) * (size_t)n_images, (hipStream_t)stream));
-    MT_HIP(hipMemsetAsync(overflow_dev, 0, sizeof(int32_t), (hipStream_t)stream));
+    MQ_HIP(hipMemsetAsync(count_dev, 0, sizeof(int32_t) * (size_t)n_images, (hipStream_t)stream));
+    MQ_HIP(hipMemsetAsync(overflow_dev, 0, sizeof(int32_t), (hipStream_t)stream));
     if (n_levels == 0) return MQ_OK;
     if (!in_dev || !levels_dev || !level_scale_dev || !weights_dev || !rec_dev || !idx_dev || !sub_dev || cap <= 0 || max_tiles <= 0 ||
         n_levels > 65535 || in_floats <= 0 || (maps_dev && maps_floats <= 0))
@@ -593,8 +585,7 @@ int mq_mtcnn_pnet_f32(const float* in_dev, int64_t in_floats, const int64_t* lev
     pnet_kernel<<<dim3((unsigned)max_tiles, (unsigned)n_levels), 256, 0, (hipStream_t)stream>>>(
         in_dev, in_floats, levels_dev, level_scale_dev, weights_dev, threshold, n_images, cap, rec_dev, idx_dev, sub_dev, count_dev,
         overflow_dev, maps_dev, maps_floats);
-    MT_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 size_t mq_mtcnn_nms_workspace_bytes(int64_t n_total) { return n_total > 0 ? (size_t)n_total * 9 * 4 : 0; }
@@ -614,8 +605,7 @@ int mq_mtcnn_nms_f32(const float* rec_dev, int64_t n_total, const int64_t* seg_s
     nms_kernel<<<(unsigned)n_seg, NT, 0, (hipStream_t)stream>>>(rec_dev, n_total, seg_start_dev, seg_count_dev, seg_cap, key_dev, sub_dev, score_gt,
                                                                threshold, mode == MQ_MTCNN_NMS_MIN, out_rec_dev, out_key_dev,
                                                                out_sub_dev, out_src_dev, out_count_dev, ws_f, ws_i);
-    MT_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_mtcnn_refine_f32(const float* in_rec_dev, const int64_t* seg_start_dev, const int64_t* dst_start_dev, int n_seg, int64_t total,
@@ -628,8 +618,7 @@ int mq_mtcnn_refine_f32(const float* in_rec_dev, const int64_t* seg_start_dev, c
     refine_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(in_rec_dev, seg_start_dev, dst_start_dev, n_seg, hw_dev,
                                                                                   flags, crop_size, out_cap, out_rec_dev, out_img_dev,
                                                                                   out_pad_dev, jobs_dev, valid_dev, overflow_dev);
-    MT_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_mtcnn_rnet_f32(const float* crops_dev, int64_t n, const float* weights_dev, const int32_t* valid_dev, float* rec_dev,
@@ -637,8 +626,7 @@ int mq_mtcnn_rnet_f32(const float* crops_dev, int64_t n, const float* weights_de
     if (n == 0) return MQ_OK;
     if (!crops_dev || !weights_dev || !rec_dev || n < 0 || n > 0x7fffffff) return MQ_EINVAL;
     rnet_kernel<<<(unsigned)n, RT, 0, (hipStream_t)stream>>>(crops_dev, weights_dev, valid_dev, rec_dev);
-    MT_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_mtcnn_onet_f32(const float* crops_dev, int64_t n, const float* weights_dev, const int32_t* valid_dev, float* rec_dev,
@@ -646,10 +634,10 @@ int mq_mtcnn_onet_f32(const float* crops_dev, int64_t n, const float* weights_de
     if (n == 0) return MQ_OK;
     if (!crops_dev || !weights_dev || !rec_dev || !points_dev || n < 0 || n > 0x7fffffff) return MQ_EINVAL;
     onet_kernel<<<(unsigned)n, OT, 0, (hipStream_t)stream>>>(crops_dev, weights_dev, valid_dev, rec_dev, points_dev);
-    MT_HIP(hipGetLastError());
+    MQ_HIP(hipGetLastError());
     if (flags & MQ_MTCNN_ONET_POST) {
         onet_post_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(rec_dev, points_dev, n);
-        MT_HIP(hipGetLastError());
+        MQ_HIP(hipGetLastError());
     }
     return MQ_OK;
 }

@@ -20,39 +20,16 @@
 #include <math.h>
 
 #include "../../include/meerqat_hip.h"
-
-extern "C" void mq_internal_set_hip_error(int e);
+#include "device_common.h"
+#include "host_check.h"
 
 namespace {
 
-#define READER_HIP(call)                                                              \
-    do {                                                                              \
-        hipError_t _e = (call);                                                       \
-        if (_e != hipSuccess) { mq_internal_set_hip_error((int)_e); return MQ_EHIP; } \
-    } while (0)
+using namespace mq_dev;
 
 constexpr int HEAD_WAVES = 4;  // token rows per head workgroup (one per wave)
 constexpr int RT = 1024;       // threads of a log-softmax / span workgroup
 constexpr int RW = RT / 64;
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, o), hi = __shfl_xor((uint32_t)(v >> 32), o);
-        const uint64_t w = ((uint64_t)hi << 32) | lo;
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(HEAD_WAVES * 64) void qa_head_kernel(const float* __restrict__ h, const float* __restrict__ w,
                                                                   const float* __restrict__ b, float* __restrict__ start,
@@ -178,8 +155,7 @@ int mq_reader_qa_head_f32(const float* h_dev, const float* w_dev, const float* b
     const unsigned grid = (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));
     hipLaunchKernelGGL(qa_head_kernel, dim3(grid), dim3(HEAD_WAVES * 64), 0, (hipStream_t)stream, h_dev, w_dev, b_dev, start_dev,
                        end_dev, rows, H);
-    READER_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_reader_log_softmax_f32(const float* start_logits_dev, const float* end_logits_dev, int N, int M, int L,
@@ -189,8 +165,7 @@ int mq_reader_log_softmax_f32(const float* start_logits_dev, const float* end_lo
     if (!start_logits_dev || !end_logits_dev || !start_logp_dev || !end_logp_dev || !start_p_dev || !end_p_dev) return MQ_EINVAL;
     hipLaunchKernelGGL(log_softmax_kernel, dim3((unsigned)N, 2), dim3(RT), 0, (hipStream_t)stream, start_logits_dev,
                        end_logits_dev, (int64_t)M * L, start_logp_dev, end_logp_dev, start_p_dev, end_p_dev);
-    READER_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 int mq_reader_best_spans_f32(const float* start_p_dev, const float* end_p_dev, const float* weights_dev, int N, int M, int L,
@@ -202,8 +177,7 @@ int mq_reader_best_spans_f32(const float* start_p_dev, const float* end_p_dev, c
     if (!start_p_dev || !end_p_dev || !passage_dev || !start_dev || !end_dev) return MQ_EINVAL;
     hipLaunchKernelGGL(best_spans_kernel, dim3((unsigned)N), dim3(RT), 0, (hipStream_t)stream, start_p_dev, end_p_dev, weights_dev,
                        M, L, cannot_be_first_token ? 1 : 0, passage_dev, start_dev, end_dev);
-    READER_HIP(hipGetLastError());
-    return MQ_OK;
+    return mq_launch_status();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // resnet.hip -- what a torchvision bottleneck ResNet (meerqat/image/embedding.py: `resnet50` cut before avgpool + AdaptiveMaxPool2d(1),
 // the `imagenet-RN50` column) needs beyond the ArcFace kernels of conv.hip, for gfx950.  Same conventions: NHWC, an activation that only
-// feeds convolutions is a split-bf16 (hi, lo) pair in PAIR LAYOUT ([row / 256][col / 32][256][32]), the BatchNorm behind a convolution
+// feeds convolutions is a split-bf16 (hi, lo) pair in PAIR LAYOUT (device_common.h), the BatchNorm behind a convolution
 // is folded into its weights and bias on the host, elementwise work rides on the epilogue of the kernel that PRODUCES a tensor.
 //   stem7x7_pool_kernel   conv 7 x 7 / 2 (3 -> 64, pad 3) + folded bn1 + ReLU + max-pool 3 x 3 / 2 (pad 1) in one pass on the vector
 //                         ALU: reads fp32 NCHW pixels, writes the POOLED tensor as a pair -- the un-pooled 112 x 112 x 64 tensor (3.2 MB
@@ -12,45 +12,17 @@
 //                         relu(acc + bias + shortcut) -> fp32 (the next shortcut / the pooled head's input) and -> pair (the next conv1).
 //   pool_hw_kernel        global max / mean over the H W pixels of the last fp32 [B H W, C] tensor -> [B, C].
 // The 3 x 3 convolutions of the bottlenecks are mq_conv3x3_pair_f32 (conv.hip) unchanged, with a zero PReLU slope = ReLU.
+// The tile -> XCD mapping and the three-product K step that conv1x1_x3s_kernel shares with conv3x3_x3s_kernel are x3_tile.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/meerqat_hip.h"
-#include "launch_attr.h"
+#include "host_check.h"
+#include "x3_tile.h"
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) char lds_char;
-
-// element (row, col) of a pair [M, K] (encoder.hip, PAIR LAYOUT)
-__device__ __forceinline__ size_t pair_index(size_t row, int col, int K) {
-    return ((row >> 8) * (size_t)(K >> 5) + (size_t)(col >> 5)) * (256 * 32) + ((row & 255) << 5) + (size_t)(col & 31);
-}
-
-__device__ __forceinline__ void split8(const float (&t)[8], bf16x8_t& h8, bf16x8_t& l8) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h = (__bf16)t[e];
-        h8[e] = h;
-        l8[e] = (__bf16)(t[e] - (float)h);
-    }
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(unsigned long)(lds_char*)p; }
-// one 1-KiB LDS-DMA piece, LDS destination lds_dst (wave-uniform) + lane * 16: wave-uniform base + per-lane byte offset ...
-__device__ __forceinline__ void dma16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// ... or a 64-bit source address per lane (the gather)
-__device__ __forceinline__ void dma16v(const void* lane_ptr, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_ptr), "s"(lds_dst) : "memory");
-}
+using namespace mq_dev;
 
 // ---- 1 x 1 convolution on a pair ---------------------------------------------------------------------------------------------------
 // C[M = B Ho Wo, N] = A[M, C] . W[N, C]^T, A row m = input pixel (b, ho s, wo s) of the input pair: K step cb of an output pixel is the 64
@@ -77,13 +49,8 @@ __global__ __launch_bounds__(1024) void conv1x1_x3s_kernel(const C1Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w / CG, wc = w % CG;
-    // workgroup b runs on XCD b & 7; each XCD takes a contiguous range of row blocks and all column tiles of a row block (the A rows
-    // of a row block reach that XCD's L2 once), as in conv3x3_x3s_kernel
-    const int b = (int)blockIdx.x;
-    const int per = (a.ntm + 7) >> 3;
-    const int mt = __builtin_amdgcn_readfirstlane((b & 7) * per + (b >> 3) / a.ntn);
-    const int nt = __builtin_amdgcn_readfirstlane((b >> 3) % a.ntn);
-    if ((b >> 3) / a.ntn >= per || mt >= a.ntm) return;
+    int mt, nt;
+    if (!xcd_tile((int)blockIdx.x, a.ntm, a.ntn, &mt, &nt)) return;
     const int m0 = mt * MT, n0 = nt * NT;
     const int CB = a.C >> 5;
 
@@ -147,40 +114,14 @@ __global__ __launch_bounds__(1024) void conv1x1_x3s_kernel(const C1Args a) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (kb + 1 < CB) issue(kb + 1, stage ^ 1);
-        const char* as = ard + stage * STAGE;
-        const char* ws = wrd + stage * STAGE;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int o = ((2 * m + kg) ^ sww) * 16;
-            bf16x8_t ah[2], al[2], wh[NF], wl[NF];
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                ah[x] = *reinterpret_cast<const bf16x8_t*>(as + x * 32 * 64 + o);
-                al[x] = *reinterpret_cast<const bf16x8_t*>(as + A_BYTES + x * 32 * 64 + o);
-            }
-#pragma unroll
-            for (int y = 0; y < NF; ++y) {
-                wh[y] = *reinterpret_cast<const bf16x8_t*>(ws + y * 32 * 64 + o);
-                wl[y] = *reinterpret_cast<const bf16x8_t*>(ws + W_BYTES + y * 32 * 64 + o);
-            }
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[x], wh[y], acc[x][y], 0, 0, 0);
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[x], wl[y], acc[x][y], 0, 0, 0);
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < NF; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[x], wh[y], acc[x][y], 0, 0, 0);
-        }
+        x3_step<NF>(ard + stage * STAGE, wrd + stage * STAGE, A_BYTES, W_BYTES, kg, sww, acc);
         stage ^= 1;
     }
 
     // ---- epilogue: one 32 x 32 accumulator at a time through LDS (4 KiB per wave), so that a lane ends up with eight consecutive
-    // columns of one row: 16-byte loads and stores
+    // columns of one row: 16-byte loads and stores.
+    // The walk is spelled out in each kernel that has it (here, conv.hip, resnet.hip, encoder.hip): shared as one function that takes
+    // the per-element operations as functors, it changes the kernels' assembly.
     __syncthreads();  // every wave has read its last operands
     float* Ot = reinterpret_cast<float*>(smem) + w * 1024;
 #pragma unroll
@@ -229,12 +170,6 @@ __global__ __launch_bounds__(1024) void conv1x1_x3s_kernel(const C1Args a) {
         }
 }
 
-#define RESNET_HIP(call)                                \
-    do {                                                \
-        hipError_t _e = (call);                         \
-        if (_e != hipSuccess) return MQ_EHIP;           \
-    } while (0)
-
 template <int RG, int WN>
 int launch_conv1x1(C1Args a, hipStream_t st) {
     constexpr int CG = 16 / RG, MT = 64 * RG, NT = WN * CG;
@@ -244,9 +179,9 @@ int launch_conv1x1(C1Args a, hipStream_t st) {
     a.ntm = (a.M + MT - 1) / MT;
     a.ntn = a.N / NT;
     const int ntiles = ((a.ntm + 7) >> 3) * 8 * a.ntn;
-    MQ_DYNAMIC_LDS_WITH(RESNET_HIP, LDS, conv1x1_x3s_kernel<RG, WN>);
+    MQ_DYNAMIC_LDS(LDS, conv1x1_x3s_kernel<RG, WN>);
     hipLaunchKernelGGL((conv1x1_x3s_kernel<RG, WN>), dim3((unsigned)ntiles), dim3(1024), LDS, st, a);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 // ---- the stem: conv 7 x 7 / 2 pad 3 (3 -> 64) + bias (bn1 folded) + ReLU + max-pool 3 x 3 / 2 pad 1 ---------------------------------
@@ -409,7 +344,7 @@ int mq_stem_conv7x7_pool_f32(const float* x_dev, int B, int H, int W, const floa
     if ((size_t)B * 3 * H * W >= 0x7FFFFFFFull * 4 || (units + 31) / 32 > 0x7FFFFFFFull) return MQ_EUNSUPPORTED;
     hipLaunchKernelGGL(stem7x7_pool_kernel, dim3((unsigned)((units + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, wt_dev,
                        bias_dev, (unsigned short*)Ph_dev, (unsigned short*)Pl_dev, B, H, W);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 int mq_pool_hw_f32(const float* X_dev, int B, int HW, int C, int mode, float* out_dev, void* stream) {
@@ -418,7 +353,7 @@ int mq_pool_hw_f32(const float* X_dev, int B, int HW, int C, int mode, float* ou
     if (mode != MQ_POOL_MAX && mode != MQ_POOL_MEAN) return MQ_EINVAL;
     hipLaunchKernelGGL(pool_hw_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, X_dev, HW, C,
                        mode == MQ_POOL_MEAN, out_dev);
-    return hipGetLastError() == hipSuccess ? MQ_OK : MQ_EHIP;
+    return mq_launch_status();
 }
 
 }  // extern "C"
