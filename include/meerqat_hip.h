@@ -219,19 +219,26 @@ int mq_knn_screen_stats(int64_t N, int d, int nq, int k, const void *ws_dev, int
 #define MQ_SCAN_KIND_STREAM 2
 int mq_knn_screen_scan_kind(int64_t N, int d, int nq, int k, int metric);
 /* Process-wide A/B switches of the search paths.  Their first values come from the environment, read ONCE (MQ_KNN_SMALL,
- * MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS); a running process flips them with mq_knn_set_option (atomic; a search already in
+ * MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS, MQ_KNN_SCAN_MFMA); a running process flips them with mq_knn_set_option (atomic; a search already in
  * its planning step may still see the old value), never by editing the environment.  Values are >= 0.
  *   MQ_KNN_OPT_SMALL_SCAN        1 (default): one query tile may be served by the streaming kernel; 0: always the tile kernel
  *   MQ_KNN_OPT_SMALL_MIN_TILES   the streaming kernel's floor of 32-row tiles per workgroup; 0 (default) = the built-in 8
  *   MQ_KNN_OPT_PARTITIONS        1 (default): 225 <= k <= 1792 is served over row ranges; 0: exact rounds
  *   MQ_KNN_OPT_SMALL_WAVES       retired (it chose round 4's one-wave-per-SIMD streaming kernel, since removed): still accepted
  *                                and stored, 8 at start, read by nothing -- kept so that old callers do not break
+ *   MQ_KNN_OPT_SCAN_MFMA         the tile kernel's matrix instruction, for measuring one against the other in one process:
+ *                                0: v_mfma_f32_32x32x16_bf16, 1 (default): v_mfma_f32_16x16x32_bf16 -- same pools, same results,
+ *                                the chip holds a higher clock under the second (profiles/r07_notes.md); first value from
+ *                                MQ_KNN_SCAN_MFMA, else MQ_KNN_SCAN_MFMA_DEFAULT.  The 32x32x16 instance stays for one release
+ *                                as the A/B twin
  * mq_knn_set_option returns the previous value, mq_knn_get_option the current one; MQ_EINVAL for an unknown key / negative value. */
 #define MQ_KNN_OPT_SMALL_SCAN 0
 #define MQ_KNN_OPT_SMALL_MIN_TILES 1
 #define MQ_KNN_OPT_PARTITIONS 2
 #define MQ_KNN_OPT_SMALL_WAVES 3
-#define MQ_KNN_OPT_COUNT 4
+#define MQ_KNN_OPT_SCAN_MFMA 4
+#define MQ_KNN_OPT_COUNT 5
+#define MQ_KNN_SCAN_MFMA_DEFAULT 1
 int mq_knn_set_option(int key, int value);
 int mq_knn_get_option(int key);
 

@@ -145,6 +145,7 @@ SIGNATURES = {
 
 
 KNN_OPT_SMALL_SCAN, KNN_OPT_SMALL_MIN_TILES, KNN_OPT_PARTITIONS, KNN_OPT_SMALL_WAVES = 0, 1, 2, 3  # MQ_KNN_OPT_* (include/meerqat_hip.h; SMALL_WAVES: retired, no effect)
+KNN_OPT_SCAN_MFMA = 4  # the tile kernel's MFMA: 0 = 32x32x16, 1 = 16x16x32
 
 
 GEMM_OPT_WIDE, GEMM_OPT_STAGGER = 0, 1  # MQ_GEMM_OPT_*

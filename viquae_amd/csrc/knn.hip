@@ -42,7 +42,7 @@ namespace {
 using namespace mq_dev;
 
 // A/B switches of the search paths (mq_knn_set_option, include/meerqat_hip.h): process-wide atomics whose FIRST values come
-// from the environment (MQ_KNN_SMALL, MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS), read once.  Tests and bench.py flip them
+// from the environment (MQ_KNN_SMALL, MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS, MQ_KNN_SCAN_MFMA), read once.  Tests and bench.py flip them
 // through the setter: no getenv() on the search path (it races with a putenv from another thread), one rule for all three.
 std::atomic<int> g_knn_opt[MQ_KNN_OPT_COUNT];
 std::once_flag g_knn_opt_once;
@@ -53,6 +53,7 @@ void knn_opt_init() {
         g_knn_opt[MQ_KNN_OPT_SMALL_MIN_TILES].store((e = getenv("MQ_KNN_SMALL_MIN_TILES")) ? atoi(e) : 0);  // 0: the built-in floor
         g_knn_opt[MQ_KNN_OPT_PARTITIONS].store((e = getenv("MQ_KNN_PARTITIONS")) ? (atoi(e) != 0) : 1);
         g_knn_opt[MQ_KNN_OPT_SMALL_WAVES].store(8);  // retired: stored, read by nothing (include/meerqat_hip.h)
+        g_knn_opt[MQ_KNN_OPT_SCAN_MFMA].store((e = getenv("MQ_KNN_SCAN_MFMA")) ? (atoi(e) != 0) : MQ_KNN_SCAN_MFMA_DEFAULT);
     });
 }
 inline int knn_opt(int key) {
@@ -988,7 +989,7 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 // per-wave timestamps through the environment; the shipped library never turns an environment variable
 // into a pointer.
 inline unsigned long long* dbg_ptr() {
-#ifdef MQ_TIMING
+#if defined(MQ_TIMING) || defined(MQ_CLOCK)
     const char* e = getenv("MQ_DBG_PTR");
     return e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr;
 #else
@@ -1709,7 +1710,10 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
             sa.nkb_copy = dp / SBK;
             const int rc = launch_small_scan(sa, small_nkb, g.S, st);
             if (rc != MQ_OK) return rc;
-        } else {
+        } else if (knn_opt(MQ_KNN_OPT_SCAN_MFMA)) {  // the tile kernel on 16x16x32 MFMAs
+            MQ_DYNAMIC_LDS(S_LDS_TOTAL, screen_scan16_kernel);
+            hipLaunchKernelGGL(screen_scan16_kernel, dim3((unsigned)(g.nqt * g.S)), dim3(1024), S_LDS_TOTAL, st, a);
+        } else {  // ... on 32x32x16 MFMAs
             MQ_DYNAMIC_LDS(S_LDS_TOTAL, screen_scan_kernel);
             hipLaunchKernelGGL(screen_scan_kernel, dim3((unsigned)(g.nqt * g.S)), dim3(1024), S_LDS_TOTAL, st, a);
         }

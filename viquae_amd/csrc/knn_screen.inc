@@ -2,7 +2,8 @@
 //
 // The exact scan (knn_scan_kernel) is bound by the fp32 matrix pipe (157 TFLOP/s).  This path gets the
 // SAME bit-exact result faster:
-//   1. screen_scan_kernel: S~ = bf16(X) . bf16(Q)^T on v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate)
+//   1. screen_scan_kernel / screen_scan16_kernel: S~ = bf16(X) . bf16(Q)^T on v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16
+//      (16x the fp32 MFMA rate; the second is the default: same cycles, the chip holds a higher clock under it)
 //      over a bf16 copy of the KB, with a pooled selection under a RELAXED threshold: a row is kept while
 //      S~ >= tau - margin_q, where tau is ANY lower bound of the final k-th best S~ (the k-th largest of the
 //      query's stripe maxima across all slabs, or a slab pool's own k-th best) and margin_q = 2*eps_q bounds
@@ -470,7 +471,14 @@ __device__ __forceinline__ int compact_pool_relaxed(u64* __restrict__ P, int* __
 }
 
 
-__global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
+// SHAPE selects the matrix instruction of the K loop and, with it, the accumulator layout the selection epilogue walks:
+//   SCAN_MFMA_32  v_mfma_f32_32x32x16_bf16, four f32x16 accumulators per wave (2 x 2 sub-tiles of 32 x 32)
+//   SCAN_MFMA_16  v_mfma_f32_16x16x32_bf16, sixteen f32x4 accumulators per wave (4 x 4 sub-tiles of 16 x 16)
+// Same waves, wave tile, stages, LDS image, DMA and barrier; the same pools, counters, stripes and thresholds come out, so
+// nothing behind the scan can tell the two apart (MQ_KNN_OPT_SCAN_MFMA picks the instance per launch).
+constexpr int SCAN_MFMA_32 = 0, SCAN_MFMA_16 = 1;
+template <int SHAPE>
+__device__ __forceinline__ void screen_scan_body(const ScreenArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* scnt = reinterpret_cast<int*>(smem + S_LDS_CNT);  // [256][8]
     float* thr = reinterpret_cast<float*>(scnt + TQ * NSL);
@@ -541,7 +549,9 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
     };
 
     // MFMA 32x32x16 bf16 operands: lane (i = lane&31, kg = lane>>5) holds k = 8*kg .. 8*kg+7 of row i
-    const int i = lane & 31, kg = lane >> 5;
+    // MFMA 16x16x32 bf16 operands: lane (i = lane&15, kg = lane>>4) holds k = 8*kg .. 8*kg+7 of row i; the sub-tiles' rows are
+    // 16 apart, so (row >> 1) & 7 = (i >> 1) & 7 stays the swizzle term
+    const int i = SHAPE == SCAN_MFMA_16 ? lane & 15 : lane & 31, kg = SHAPE == SCAN_MFMA_16 ? lane >> 4 : lane >> 5;
     const int sw = (i >> 1) & 7;
     const char* xrd = smem + S_LDS_X + (64 * wr + i) * 128;
     const char* qrd = smem + S_LDS_Q + (64 * wc + i) * 128;
@@ -552,12 +562,15 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
     // tight: ~0.3 sigma under the true k-th best) lower bound of the global k-th best long before any pool holds k
     // good rows -- the per-slab pools alone only know the slab's own k-th best.  Maxima only grow, so stale reads
     // by other workgroups are still valid bounds.
+    // 16x16x32: a stripe belongs to a (lane, query column) instead -- rows 16 a + 4 kg + reg (a = 0 .. 3) of the wave's 64,
+    // again 16 rows of every chunk, stripe wr * 4 + kg of the query; that arm calls the four maxima rmc0 .. rmc3.
     float rm00 = -INFINITY, rm10 = -INFINITY, rm01 = -INFINITY, rm11 = -INFINITY;
     // When there are more than 16 slabs, a slab's 16 stripes fold into sps = 256 / S slots (atomic max): a slot then
     // holds the maximum over a union of stripes -- still disjoint row sets.
     const int ms = a.ms, sps = a.sps;
     const bool publish = slab * sps + sps <= ms;
     // stripe -> slot offsets of this wave's two lane halves (kg = 0 / 1), as scalars: sps need not be a power of two
+    // 16x16x32: the same four values are the slots of the wave's four lane quarters kg = 0, 1, 2, 3 (a0, a1, b0, b1).
     const int so_a0 = __builtin_amdgcn_readfirstlane((wr * 4) % sps), so_a1 = __builtin_amdgcn_readfirstlane((wr * 4 + 1) % sps);
     const int so_b0 = __builtin_amdgcn_readfirstlane((wr * 4 + 2) % sps), so_b1 = __builtin_amdgcn_readfirstlane((wr * 4 + 3) % sps);
     // Everything else the selection epilogue needs per lane (its two queries, their stripe slots, pool slices) is
@@ -671,6 +684,12 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
     asm volatile("" ::: "memory");
     issue_next(1);
     int stage = 0;
+#ifdef MQ_CLOCK
+    // diagnostic build (tools/scan_clock.py, tools/scan_compactions.py; three words per workgroup, 4096 workgroups): the clock the chip holds while this kernel runs = shader-clock ticks per 100 MHz
+    // wall-clock tick, one stamp pair around the whole chunk loop; the stamps go to a.dbg, which nothing else reads
+    const unsigned long long ck_s0_ = __builtin_amdgcn_s_memtime(), ck_r0_ = __builtin_amdgcn_s_memrealtime();
+    unsigned long long ck_rounds_ = 0;  // compaction rounds of this workgroup (tools/scan_compactions.py)
+#endif
 #ifdef MQ_TIMING
     unsigned long long tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #define MQ_TS(i) MQ_T(i)
@@ -683,64 +702,155 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
     for (int pass = (c0 < c1 ? -1 : 0); pass < c1 - c0; ++pass) {
         const bool warm = pass < 0;
         const int c = c0 + (warm ? 0 : pass);
-        f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};
+        f32x16 acc00 = {0}, acc01 = {0}, acc10 = {0}, acc11 = {0};  // SCAN_MFMA_32
+        // SCAN_MFMA_16: c<a><b> = rows 16 a .. of the wave's 64 x queries 16 b ..; sixteen named values (an array indexed by
+        // loop variables invites the compiler to keep it in scratch)
+        f32x4_t c00 = {0}, c10 = {0}, c20 = {0}, c30 = {0}, c01 = {0}, c11 = {0}, c21 = {0}, c31 = {0};
+        f32x4_t c02 = {0}, c12 = {0}, c22 = {0}, c32 = {0}, c03 = {0}, c13 = {0}, c23 = {0}, c33 = {0};
 #define MQ_LDF(p) (*reinterpret_cast<const bf16x8_t*>(p))
-        // m = 0 operands of the chunk's first step (its stage landed before the barrier of the previous step)
-        const int off0 = ((0 + kg) ^ sw) * 16;
-        bf16x8_t pxa0 = MQ_LDF(xrd + stage * S_OP_BYTES + off0), pxa1 = MQ_LDF(xrd + stage * S_OP_BYTES + 32 * 128 + off0);
-        bf16x8_t pqb0 = MQ_LDF(qrd + stage * S_OP_BYTES + off0), pqb1 = MQ_LDF(qrd + stage * S_OP_BYTES + 32 * 128 + off0);
-        for (int kb = 0; kb < nkb; ++kb) {
-            const char* xs = xrd + stage * S_OP_BYTES;
-            const char* qs = qrd + stage * S_OP_BYTES;
-            if (kb == 0) {
-                // the chunk's first MFMAs take the constant 0 as their C operand: no 64 v_mov per wave and chunk to clear the
-                // accumulators while the matrix pipe sits idle between two chunks
-                const f32x16 zero16 = {0};
-                acc00 = MQ_SMFMA(pxa0, pqb0, zero16, 0, 0, 0);
-                acc01 = MQ_SMFMA(pxa0, pqb1, zero16, 0, 0, 0);
-                acc10 = MQ_SMFMA(pxa1, pqb0, zero16, 0, 0, 0);
-                acc11 = MQ_SMFMA(pxa1, pqb1, zero16, 0, 0, 0);
-            } else {
-                acc00 = MQ_SMFMA(pxa0, pqb0, acc00, 0, 0, 0);
-                acc01 = MQ_SMFMA(pxa0, pqb1, acc01, 0, 0, 0);
-                acc10 = MQ_SMFMA(pxa1, pqb0, acc10, 0, 0, 0);
-                acc11 = MQ_SMFMA(pxa1, pqb1, acc11, 0, 0, 0);
-            }
+        if constexpr (SHAPE == SCAN_MFMA_32) {
+            // m = 0 operands of the chunk's first step (its stage landed before the barrier of the previous step)
+            const int off0 = ((0 + kg) ^ sw) * 16;
+            bf16x8_t pxa0 = MQ_LDF(xrd + stage * S_OP_BYTES + off0), pxa1 = MQ_LDF(xrd + stage * S_OP_BYTES + 32 * 128 + off0);
+            bf16x8_t pqb0 = MQ_LDF(qrd + stage * S_OP_BYTES + off0), pqb1 = MQ_LDF(qrd + stage * S_OP_BYTES + 32 * 128 + off0);
+            for (int kb = 0; kb < nkb; ++kb) {
+                const char* xs = xrd + stage * S_OP_BYTES;
+                const char* qs = qrd + stage * S_OP_BYTES;
+                if (kb == 0) {
+                    // the chunk's first MFMAs take the constant 0 as their C operand: no 64 v_mov per wave and chunk to clear the
+                    // accumulators while the matrix pipe sits idle between two chunks
+                    const f32x16 zero16 = {0};
+                    acc00 = MQ_SMFMA(pxa0, pqb0, zero16, 0, 0, 0);
+                    acc01 = MQ_SMFMA(pxa0, pqb1, zero16, 0, 0, 0);
+                    acc10 = MQ_SMFMA(pxa1, pqb0, zero16, 0, 0, 0);
+                    acc11 = MQ_SMFMA(pxa1, pqb1, zero16, 0, 0, 0);
+                } else {
+                    acc00 = MQ_SMFMA(pxa0, pqb0, acc00, 0, 0, 0);
+                    acc01 = MQ_SMFMA(pxa0, pqb1, acc01, 0, 0, 0);
+                    acc10 = MQ_SMFMA(pxa1, pqb0, acc10, 0, 0, 0);
+                    acc11 = MQ_SMFMA(pxa1, pqb1, acc11, 0, 0, 0);
+                }
 #pragma unroll
-            for (int m = 1; m < SBK / 16 - 1; ++m) {
-                const int off = ((2 * m + kg) ^ sw) * 16;
-                const bf16x8_t xa0 = MQ_LDF(xs + off), xa1 = MQ_LDF(xs + 32 * 128 + off);
-                const bf16x8_t qb0 = MQ_LDF(qs + off), qb1 = MQ_LDF(qs + 32 * 128 + off);
-                acc00 = MQ_SMFMA(xa0, qb0, acc00, 0, 0, 0);
-                acc01 = MQ_SMFMA(xa0, qb1, acc01, 0, 0, 0);
-                acc10 = MQ_SMFMA(xa1, qb0, acc10, 0, 0, 0);
-                acc11 = MQ_SMFMA(xa1, qb1, acc11, 0, 0, 0);
+                for (int m = 1; m < SBK / 16 - 1; ++m) {
+                    const int off = ((2 * m + kg) ^ sw) * 16;
+                    const bf16x8_t xa0 = MQ_LDF(xs + off), xa1 = MQ_LDF(xs + 32 * 128 + off);
+                    const bf16x8_t qb0 = MQ_LDF(qs + off), qb1 = MQ_LDF(qs + 32 * 128 + off);
+                    acc00 = MQ_SMFMA(xa0, qb0, acc00, 0, 0, 0);
+                    acc01 = MQ_SMFMA(xa0, qb1, acc01, 0, 0, 0);
+                    acc10 = MQ_SMFMA(xa1, qb0, acc10, 0, 0, 0);
+                    acc11 = MQ_SMFMA(xa1, qb1, acc11, 0, 0, 0);
+                }
+                {
+                    const int off = ((2 * (SBK / 16 - 1) + kg) ^ sw) * 16;
+                    const bf16x8_t xa0 = MQ_LDF(xs + off), xa1 = MQ_LDF(xs + 32 * 128 + off);
+                    const bf16x8_t qb0 = MQ_LDF(qs + off), qb1 = MQ_LDF(qs + 32 * 128 + off);
+                    acc00 = MQ_SMFMA(xa0, qb0, acc00, 0, 0, 0);
+                    acc01 = MQ_SMFMA(xa0, qb1, acc01, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    // every LDS read of this wave from the current stage has returned; its DMA pieces of the next stage have landed
+                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc10 = MQ_SMFMA(xa1, qb0, acc10, 0, 0, 0);
+                    acc11 = MQ_SMFMA(xa1, qb1, acc11, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                const int freed = stage;
+                stage ^= 1;
+                if (kb + 1 < nkb) {  // the next step's first operands, from the stage that has just been declared complete
+                    pxa0 = MQ_LDF(xrd + stage * S_OP_BYTES + off0); pxa1 = MQ_LDF(xrd + stage * S_OP_BYTES + 32 * 128 + off0);
+                    pqb0 = MQ_LDF(qrd + stage * S_OP_BYTES + off0); pqb1 = MQ_LDF(qrd + stage * S_OP_BYTES + 32 * 128 + off0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                issue_next(freed);
+                __builtin_amdgcn_sched_barrier(0);
             }
+        } else {
+            // 16x16x32: a K step is two 32-deep half-steps h; in half-step h the lane reads chunk (4 h + kg) ^ sw of rows
+            // 16 a + i (X: the A fragment of row block a) and 16 b + i (Q: the B fragment of column b).  A half-step is walked
+            // column by column: its four A fragments stay live, the B fragments alternate between qe and qo, read one column
+            // ahead.  Registers: 64 accumulators + 16 (A) + 8 (B) + 8 that let the NEXT half-step's fragments arrive in time --
+            // 96, what the 32x32x16 loop holds behind its barrier.  Half-step 0 keeps its A fragments in x0 .. x3 and reads
+            // e0, e1 = A0, A1 of half-step 1 meanwhile; its last column issues rows 0, 1 first and reads A2, A3 of half-step 1
+            // into the x0, x1 they leave.  Half-step 1 runs on (e0, e1, x0, x1); behind the barrier -- as above, before the
+            // step's last four MFMAs -- x2, x3 and the first B fragment of the next step are read, then x0, x1 once the
+            // last column's rows 2, 3 have issued, and the next step's first column takes rows 2, 3 first.
+#define MQ_M16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
+#define MQ_ACC(x) x
+#define MQ_ZERO(x) zero4
+#define MQ_FR(base, r, off) MQ_LDF((base) + (r) * 16 * 128 + (off))
+#define MQ_MM(a_, b_, A, B, C) c##a_##b_ = MQ_M16(A, B, C(c##a_##b_), 0, 0, 0);
+#define MQ_PIN __builtin_amdgcn_sched_barrier(0);  // the order below IS the register plan: nothing moves across a column
+#define MQ_HALF0(C)                                                                               \
+    qo = MQ_FR(qs, 1, off0); e0 = MQ_FR(xs, 0, off1); e1 = MQ_FR(xs, 1, off1);                    \
+    MQ_MM(2, 0, x2, qe, C) MQ_MM(3, 0, x3, qe, C) MQ_MM(0, 0, x0, qe, C) MQ_MM(1, 0, x1, qe, C)   \
+    MQ_PIN qe = MQ_FR(qs, 2, off0);                                                               \
+    MQ_MM(0, 1, x0, qo, C) MQ_MM(1, 1, x1, qo, C) MQ_MM(2, 1, x2, qo, C) MQ_MM(3, 1, x3, qo, C)   \
+    MQ_PIN qo = MQ_FR(qs, 3, off0);                                                               \
+    MQ_MM(0, 2, x0, qe, C) MQ_MM(1, 2, x1, qe, C) MQ_MM(2, 2, x2, qe, C) MQ_MM(3, 2, x3, qe, C)   \
+    MQ_PIN qe = MQ_FR(qs, 0, off1);                                                               \
+    MQ_MM(0, 3, x0, qo, C) MQ_MM(1, 3, x1, qo, C)                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                            \
+    x0 = MQ_FR(xs, 2, off1); x1 = MQ_FR(xs, 3, off1);                                             \
+    MQ_MM(2, 3, x2, qo, C) MQ_MM(3, 3, x3, qo, C)                                                 \
+    __builtin_amdgcn_sched_barrier(0);
+            const int offk = (kg ^ sw) * 16;  // chunk (0 + kg) ^ sw; half-step 1 reads chunk (4 + kg) ^ sw, 64 bytes to the side
+            const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+            bf16x8_t x0, x1, x2, x3, e0, e1, qe, qo;
             {
-                const int off = ((2 * (SBK / 16 - 1) + kg) ^ sw) * 16;
-                const bf16x8_t xa0 = MQ_LDF(xs + off), xa1 = MQ_LDF(xs + 32 * 128 + off);
-                const bf16x8_t qb0 = MQ_LDF(qs + off), qb1 = MQ_LDF(qs + 32 * 128 + off);
-                acc00 = MQ_SMFMA(xa0, qb0, acc00, 0, 0, 0);
-                acc01 = MQ_SMFMA(xa0, qb1, acc01, 0, 0, 0);
+                const int off0 = offk;
+                const char* xs = xrd + stage * S_OP_BYTES;
+                x2 = MQ_FR(xs, 2, off0); x3 = MQ_FR(xs, 3, off0); qe = MQ_FR(qrd + stage * S_OP_BYTES, 0, off0);
+                x0 = MQ_FR(xs, 0, off0); x1 = MQ_FR(xs, 1, off0);
+            }
+            for (int kb = 0; kb < nkb; ++kb) {
+                const char* xs = xrd + stage * S_OP_BYTES;
+                const char* qs = qrd + stage * S_OP_BYTES;
+                // (an opaque copy per step: hoisted out of the loop, the second offset and the sums it enters are registers
+                // the loop does not have)
+                int off0 = offk;
+                asm volatile("" : "+v"(off0));
+                const int off1 = off0 ^ 64;
+                if (kb == 0) {  // C = the constant 0, as above
+                    MQ_HALF0(MQ_ZERO)
+                } else {
+                    MQ_HALF0(MQ_ACC)
+                }
+                qo = MQ_FR(qs, 1, off1);
+                MQ_MM(0, 0, e0, qe, MQ_ACC) MQ_MM(1, 0, e1, qe, MQ_ACC) MQ_MM(2, 0, x0, qe, MQ_ACC) MQ_MM(3, 0, x1, qe, MQ_ACC)
+                MQ_PIN qe = MQ_FR(qs, 2, off1);
+                MQ_MM(0, 1, e0, qo, MQ_ACC) MQ_MM(1, 1, e1, qo, MQ_ACC) MQ_MM(2, 1, x0, qo, MQ_ACC) MQ_MM(3, 1, x1, qo, MQ_ACC)
+                MQ_PIN qo = MQ_FR(qs, 3, off1);
+                MQ_MM(0, 2, e0, qe, MQ_ACC) MQ_MM(1, 2, e1, qe, MQ_ACC) MQ_MM(2, 2, x0, qe, MQ_ACC) MQ_MM(3, 2, x1, qe, MQ_ACC)
                 __builtin_amdgcn_sched_barrier(0);
                 // every LDS read of this wave from the current stage has returned; its DMA pieces of the next stage have landed
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-                acc10 = MQ_SMFMA(xa1, qb0, acc10, 0, 0, 0);
-                acc11 = MQ_SMFMA(xa1, qb1, acc11, 0, 0, 0);
+                const int freed = stage;
+                stage ^= 1;
+                // the next step's first fragments, from the stage that has just been declared complete (after the chunk's last
+                // step these are the next chunk's, read again at its top: five reads per chunk for a loop without a branch;
+                // after the slab's LAST chunk no DMA has filled that stage -- the reads are inside LDS and their values dead)
+                x2 = MQ_FR(xrd + stage * S_OP_BYTES, 2, off0); x3 = MQ_FR(xrd + stage * S_OP_BYTES, 3, off0);
+                qe = MQ_FR(qrd + stage * S_OP_BYTES, 0, off0);
+                MQ_MM(2, 3, x0, qo, MQ_ACC) MQ_MM(3, 3, x1, qo, MQ_ACC)
+                __builtin_amdgcn_sched_barrier(0);
+                x0 = MQ_FR(xrd + stage * S_OP_BYTES, 0, off0); x1 = MQ_FR(xrd + stage * S_OP_BYTES, 1, off0);
+                MQ_MM(0, 3, e0, qo, MQ_ACC) MQ_MM(1, 3, e1, qo, MQ_ACC)
+                __builtin_amdgcn_sched_barrier(0);
+                issue_next(freed);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            const int freed = stage;
-            stage ^= 1;
-            if (kb + 1 < nkb) {  // the next step's first operands, from the stage that has just been declared complete
-                pxa0 = MQ_LDF(xrd + stage * S_OP_BYTES + off0); pxa1 = MQ_LDF(xrd + stage * S_OP_BYTES + 32 * 128 + off0);
-                pqb0 = MQ_LDF(qrd + stage * S_OP_BYTES + off0); pqb1 = MQ_LDF(qrd + stage * S_OP_BYTES + 32 * 128 + off0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            issue_next(freed);
-            __builtin_amdgcn_sched_barrier(0);
+#undef MQ_HALF0
+#undef MQ_PIN
+#undef MQ_MM
+#undef MQ_FR
+#undef MQ_ZERO
+#undef MQ_ACC
+#undef MQ_M16
         }
 #undef MQ_LDF
 
@@ -752,22 +862,23 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
             etid = (int)t_;
             elane = etid & 63;
         }
-        const int ekg = elane >> 5;
-        const int q0 = wc * 64 + (elane & 31), q1 = q0 + 32;  // this lane's two queries (tile-local)
-        // this lane's stripes: (wr * 2 + ekg) * 2 (sub-tile 0) and the next one (sub-tile 1)
-        unsigned* const sm0 = a.smax + (size_t)(qt * TQ + q0) * ms + slab * sps;
-        unsigned* const sm1 = a.smax + (size_t)(qt * TQ + q1) * ms + slab * sps;
-        const int so0 = ekg ? so_b0 : so_a0, so1 = ekg ? so_b1 : so_a1;
+        const int ekg = SHAPE == SCAN_MFMA_16 ? elane >> 4 : elane >> 5;
         const unsigned rowbase = (unsigned)c * TN + wr * 64 + 4 * ekg;
         const unsigned nrows = (unsigned)a.N;
         const int rc0 = warm ? 0 : pass;  // chunk ordinal inside the slab
         const bool ragged = ((long long)c + 1) * TN > a.N;
         MQ_TS(0)
 #ifdef MQ_TIMING
-        asm volatile("" ::"v"(acc00[0]), "v"(acc01[0]), "v"(acc10[0]), "v"(acc11[15]));  // bucket 1 = wait for the last MFMAs
+        if constexpr (SHAPE == SCAN_MFMA_32) asm volatile("" ::"v"(acc00[0]), "v"(acc01[0]), "v"(acc10[0]), "v"(acc11[15]));  // bucket 1 = wait for the last MFMAs
+        else asm volatile("" ::"v"(c00[0]), "v"(c13[0]), "v"(c23[0]), "v"(c33[3]));
 #endif
         MQ_TS(1)
-        {
+        if constexpr (SHAPE == SCAN_MFMA_32) {
+            const int q0 = wc * 64 + (elane & 31), q1 = q0 + 32;  // this lane's two queries (tile-local)
+            // this lane's stripes: (wr * 2 + ekg) * 2 (sub-tile 0) and the next one (sub-tile 1)
+            unsigned* const sm0 = a.smax + (size_t)(qt * TQ + q0) * ms + slab * sps;
+            unsigned* const sm1 = a.smax + (size_t)(qt * TQ + q1) * ms + slab * sps;
+            const int so0 = ekg ? so_b0 : so_a0, so1 = ekg ? so_b1 : so_a1;
             // this lane's private slices of its two queries' pools: no atomics, the slot counters live in
             // registers during the scan
             const int sl = wr * 2 + ekg;
@@ -830,6 +941,86 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
             scnt[q1 * NSL + sl] = n1;
             if (n0 > SLCAP - 64 || n1 > SLCAP - 64) wgflag[rc0 % 3] = 1;
             if (etid == 0) wgflag[(rc0 + 1) % 3] = 0;
+        } else {
+            // 16x16 C/D map: col = lane & 15 -> query wc * 64 + 16 b + (lane & 15) of column b; row = 4 kg + reg -> KB row
+            // 64 wr + 16 a + 4 kg + reg.  A lane owns four queries and 16 rows of the chunk for each: the column's four
+            // accumulators c0b .. c3b are the 16 scores the 32 x 32 sub-tile rule above walks -- the same v_max3 tree, the
+            // same ballot-gated triples.  One column at a time, so that what a column needs (threshold, counter, pool and
+            // slot addresses) is live for that column only.
+            // Slice wr * 2 + (kg >> 1) of a query has TWO writer lanes here, lane and lane ^ 16 (kg even / odd): both hold the
+            // slice's counter n.  Per group of sites that passed its ballot the lanes swap their hit counts (one ds_swizzle);
+            // the even lane appends at n, the odd one behind the even one's hits, both advance n by the sum -- so both write
+            // the same value back to scnt.  A slice still takes at most 2 x 16 keys per chunk and query.
+            float &rmc0 = rm00, &rmc1 = rm10, &rmc2 = rm01, &rmc3 = rm11;  // running maxima of this lane's query columns 0 .. 3
+            const int qc = wc * 64 + (elane & 15);
+            const int sl = wr * 2 + (ekg >> 1);
+            const bool odd = (ekg & 1) != 0;
+            const int so = ekg == 0 ? so_a0 : ekg == 1 ? so_a1 : ekg == 2 ? so_b0 : so_b1;
+            bool full = false;
+            auto column = [&](auto rag, auto wm, auto pb, const int b, const f32x4_t& v0, const f32x4_t& v1, const f32x4_t& v2,
+                              const f32x4_t& v3, float& rmax) __attribute__((always_inline)) {
+                constexpr bool ragged = decltype(rag)::value, warm = decltype(wm)::value, publish = decltype(pb)::value;
+                const int q = qc + 16 * b;
+                const float t = thr[q];
+                const float m0 = fmaxf(fmaxf(v0[0], v0[1]), v0[2]), m1 = fmaxf(fmaxf(v0[3], v1[0]), v1[1]);
+                const float m2 = fmaxf(fmaxf(v1[2], v1[3]), v2[0]), m3 = fmaxf(fmaxf(v2[1], v2[2]), v2[3]);
+                const float m4 = fmaxf(fmaxf(v3[0], v3[1]), v3[2]);
+                const float gm = fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), v3[3]));
+                if (!ragged) {
+                    if (gm > rmax) {
+                        rmax = gm;
+                        if (publish)
+                            __hip_atomic_fetch_max(a.smax + (size_t)(qt * TQ + q) * ms + slab * sps + so, (unsigned)(make_key(gm, 0u) >> 32),
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(gm >= t) == 0ull) return;
+                }
+                if (warm) return;
+                int n = scnt[q * NSL + sl];
+                u64* __restrict__ P = mypools + (size_t)q * SPOOL + sl * SLCAP;
+                // sites (x, a, reg): score x of row rowbase + 16 a + reg; every lane of the wave gets here together
+                auto sites = [&](const float x0, const unsigned r0, const bool two, const float x1, const unsigned r1, const float x2,
+                                 const unsigned r2) __attribute__((always_inline)) {
+                    const bool h0 = (!ragged || rowbase + r0 < nrows) && x0 >= t;
+                    const bool h1 = two && (!ragged || rowbase + r1 < nrows) && x1 >= t;
+                    const bool h2 = two && (!ragged || rowbase + r2 < nrows) && x2 >= t;
+                    const int mine = (int)h0 + (int)h1 + (int)h2;
+                    const int theirs = __builtin_amdgcn_ds_swizzle(mine, 0x401F);  // lane ^ 16
+                    int at = n + (odd ? theirs : 0);
+                    if (h0) P[at++] = make_key(x0, rowbase + r0);
+                    if (h1) P[at++] = make_key(x1, rowbase + r1);
+                    if (h2) P[at++] = make_key(x2, rowbase + r2);
+                    n += mine + theirs;
+                };
+                if (ragged || __builtin_amdgcn_ballot_w64(m0 >= t) != 0ull) sites(v0[0], 0, true, v0[1], 1, v0[2], 2);
+                if (ragged || __builtin_amdgcn_ballot_w64(m1 >= t) != 0ull) sites(v0[3], 3, true, v1[0], 16, v1[1], 17);
+                if (ragged || __builtin_amdgcn_ballot_w64(m2 >= t) != 0ull) sites(v1[2], 18, true, v1[3], 19, v2[0], 32);
+                if (ragged || __builtin_amdgcn_ballot_w64(m3 >= t) != 0ull) sites(v2[1], 33, true, v2[2], 34, v2[3], 35);
+                if (ragged || __builtin_amdgcn_ballot_w64(m4 >= t) != 0ull) sites(v3[0], 48, true, v3[1], 49, v3[2], 50);
+                if (ragged || __builtin_amdgcn_ballot_w64(v3[3] >= t) != 0ull) sites(v3[3], 51, false, 0.f, 0u, 0.f, 0u);
+                scnt[q * NSL + sl] = n;
+                full |= n > SLCAP - 64;
+            };
+#define MQ_COLUMNS(RAG, WM, PB)                                      \
+    column(RAG{}, WM{}, PB{}, 0, c00, c10, c20, c30, rmc0);          \
+    column(RAG{}, WM{}, PB{}, 1, c01, c11, c21, c31, rmc1);          \
+    column(RAG{}, WM{}, PB{}, 2, c02, c12, c22, c32, rmc2);          \
+    column(RAG{}, WM{}, PB{}, 3, c03, c13, c23, c33, rmc3);
+            using T_ = std::true_type;
+            using F_ = std::false_type;
+            if (ragged) {
+                if (warm) { MQ_COLUMNS(T_, T_, F_) } else { MQ_COLUMNS(T_, F_, F_) }
+            } else if (warm) {
+                if (publish) { MQ_COLUMNS(F_, T_, T_) } else { MQ_COLUMNS(F_, T_, F_) }
+            } else if (publish) {
+                MQ_COLUMNS(F_, F_, T_)
+            } else {
+                MQ_COLUMNS(F_, F_, F_)
+            }
+#undef MQ_COLUMNS
+            MQ_TS(3)
+            if (full) wgflag[rc0 % 3] = 1;
+            if (etid == 0) wgflag[(rc0 + 1) % 3] = 0;
         }
         MQ_TS(5)
         if (warm) {
@@ -878,6 +1069,9 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
         // (<= 96 of 128 slots then, <= 128 now); the K-loop barriers in between make the flag uniform.  This chunk
         // raises flag[c % 3]; flag[(c + 1) % 3] is cleared for the next one.
         if (wgflag[(rc0 + 2) % 3]) {
+#ifdef MQ_CLOCK
+            ++ck_rounds_;
+#endif
             __syncthreads();  // vmcnt(0) of every wave + barrier: all appended keys are in L2
             for (int j = 0; j < TQ / NWAVES; ++j) {
                 const int q = w + NWAVES * j;
@@ -895,6 +1089,13 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
         MQ_TS(6)
     }
     MQ_TS_DUMP
+#ifdef MQ_CLOCK
+    if (a.dbg && tid == 0 && blockIdx.x < 4096) {
+        a.dbg[3 * blockIdx.x] = __builtin_amdgcn_s_memtime() - ck_s0_;
+        a.dbg[3 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - ck_r0_;
+        a.dbg[3 * blockIdx.x + 2] = ck_rounds_;
+    }
+#endif
     // The pools stay in their sliced layout (no end-of-slab compaction): cand_select reads slice z of a pool at
     // [z * SLCAP, z * SLCAP + count z).
     __syncthreads();
@@ -905,6 +1106,8 @@ __global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) {
         dst[1] = src[1];
     }
 }
+__global__ __launch_bounds__(1024) void screen_scan_kernel(const ScreenArgs a) { screen_scan_body<SCAN_MFMA_32>(a); }
+__global__ __launch_bounds__(1024) void screen_scan16_kernel(const ScreenArgs a) { screen_scan_body<SCAN_MFMA_16>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // candidate selection, exact re-scoring, final selection
