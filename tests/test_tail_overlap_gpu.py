@@ -75,27 +75,66 @@ def test_flagged_tiles_are_recomputed_on_the_second_stream(monkeypatch):
     assert torch.equal(I0, Ie) and torch.equal(D0, De) and torch.equal(I1, Ie) and torch.equal(D1, De)
 
 
-def test_phase_flags_through_the_c_abi():
-    """FRONT then TAIL on ONE stream = the one-call search; both bits = the one-call search; unknown bits are refused."""
+# route -> (metric, factory, l2norm form, rows, d, queries, k, planner switch for the case, scan kind the planner reports).  The
+# smallest shapes that still take the route.  The streaming scan needs 256 chunks of 256 rows (65,281 rows) whatever its floor of
+# tiles per workgroup: 65,300 rows take it under SMALL_MIN_TILES = 1 and not at the default floor of 8.  Row ranges: k = 300 is
+# P = 3 ranges of 16,896 rows, each scanned by the tile kernel.
+_PHASE_CASES = {
+    "tile-ip": (0, "Flat", "numpy", 20000, 80, 700, 10, None, "tile"),
+    "tile-l2": (1, "Flat", "numpy", 20000, 80, 700, 10, None, "tile"),
+    "tile-l2norm-faiss": (0, "L2norm,Flat", "faiss", 20000, 80, 700, 10, None, "tile"),
+    "stream-ip": (0, "Flat", "numpy", 65300, 64, 256, 100, "SMALL_MIN_TILES", "stream"),
+    "stream-l2": (1, "Flat", "numpy", 65300, 64, 256, 100, "SMALL_MIN_TILES", "stream"),
+    "row-ranges": (0, "Flat", "numpy", 50000, 64, 300, 300, None, "tile"),
+    "exact-rounds": (0, "Flat", "numpy", 9000, 64, 300, 1800, None, "none"),
+    "l2-direct": (1, "Flat", "numpy", 9000, 64, 19, 10, None, "none"),
+}
+
+
+@pytest.mark.parametrize("route", list(_PHASE_CASES))
+def test_phase_flags_through_the_c_abi(route):
+    """On every route of the screened entry: FRONT then TAIL on ONE stream = the one-call search; both bits = the one-call
+    search; unknown bits are refused.  A route the screen does not serve does everything in its FRONT call: its TAIL call alone
+    writes nothing."""
+    import contextlib
     import torch
     from viquae_amd import _lib
     from viquae_amd.index import FLAG_PHASE_FRONT, FLAG_PHASE_TAIL, MI355XFlatIndex
+    metric, factory, form, n, d, nq, k, switch, kind = _PHASE_CASES[route]
     g = torch.Generator(device="cuda").manual_seed(9)
-    X = torch.randn((20000, 80), generator=g, device="cuda")
-    Q = torch.randn((700, 80), generator=g, device="cuda")
-    idx = MI355XFlatIndex(string_factory="Flat", metric_type=0, screen=True)
+    X = torch.randn((n, d), generator=g, device="cuda")
+    Q = torch.randn((nq, d), generator=g, device="cuda")
+    idx = MI355XFlatIndex(string_factory=factory, metric_type=metric, screen=True, l2norm_form=form)
     idx.add(X)
-    D, I = idx.search_device(Q, 10)
-    spaces, tail = idx.pipeline_workspaces(700, 10)
-    main = torch.cuda.current_stream()
-    for phases in ((FLAG_PHASE_FRONT, FLAG_PHASE_TAIL), (FLAG_PHASE_FRONT | FLAG_PHASE_TAIL,)):
-        out = (torch.zeros_like(D), torch.zeros_like(I))
-        for ph in phases:
-            idx.search_phase(Q, 10, out, spaces[1], ph, main)
-        assert torch.equal(out[0], D) and torch.equal(out[1], I)
+    with _lib.knn_option(_lib.KNN_OPT_SMALL_MIN_TILES, 1) if switch == "SMALL_MIN_TILES" else contextlib.nullcontext():
+        # the case really takes the route it is named after
+        assert idx.scan_kind(nq, k) == kind
+        if switch == "SMALL_MIN_TILES":
+            with _lib.knn_option(_lib.KNN_OPT_SMALL_MIN_TILES, 0):
+                assert idx.scan_kind(nq, k) == "tile"
+        if route == "row-ranges":
+            with _lib.knn_option(_lib.KNN_OPT_PARTITIONS, 0):
+                assert idx.scan_kind(nq, k) == "none"
+        if route == "exact-rounds":
+            assert k > 1792
+        if route == "l2-direct":
+            assert nq < 20 and idx.scan_kind(20, k) == "tile"
+        D, I = idx.search_device(Q, k)
+        spaces, tail = idx.pipeline_workspaces(nq, k)
+        main = torch.cuda.current_stream()
+        for phases in ((FLAG_PHASE_FRONT, FLAG_PHASE_TAIL), (FLAG_PHASE_FRONT | FLAG_PHASE_TAIL,)):
+            out = (torch.zeros_like(D), torch.zeros_like(I))
+            for ph in phases:
+                idx.search_phase(Q, k, out, spaces[1], ph, main)
+            assert torch.equal(out[0], D) and torch.equal(out[1], I)
+        if route in ("row-ranges", "exact-rounds", "l2-direct"):
+            out = (torch.full_like(D, 12345.0), torch.full_like(I, -777))
+            idx.search_phase(Q, k, out, spaces[1], FLAG_PHASE_TAIL, main)
+            torch.cuda.synchronize()
+            assert bool((out[0] == 12345.0).all()) and bool((out[1] == -777).all())
     lib = _lib.load()
     rc = lib.mq_knn_search_screened_f32(None, idx._sqnorm.data_ptr(), idx._rowmajor.data_ptr(), idx._bf16.data_ptr(),
-                                        idx._xmax2.data_ptr(), idx.ntotal, idx.d, Q.data_ptr(), 700, 10, 0, 32, 0, D.data_ptr(),
+                                        idx._xmax2.data_ptr(), idx.ntotal, idx.d, Q.data_ptr(), nq, k, metric, 32, 0, D.data_ptr(),
                                         I.data_ptr(), spaces[0].data_ptr(), spaces[0].numel(), main.cuda_stream, None, None)
     assert rc != 0
 

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
+#include <vector>
 
 #include "../../include/meerqat_hip.h"
 #include "device_common.h"
@@ -42,8 +43,9 @@ namespace {
 using namespace mq_dev;
 
 // A/B switches of the search paths (mq_knn_set_option, include/meerqat_hip.h): process-wide atomics whose FIRST values come
-// from the environment (MQ_KNN_SMALL, MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS, MQ_KNN_SCAN_MFMA), read once.  Tests and bench.py flip them
-// through the setter: no getenv() on the search path (it races with a putenv from another thread), one rule for all three.
+// from the environment (MQ_KNN_SMALL, MQ_KNN_SMALL_MIN_TILES, MQ_KNN_PARTITIONS, MQ_KNN_SCAN_MFMA; the retired SMALL_WAVES has
+// none), read once.  Tests and bench.py flip them through the setter: no getenv() on the search path (it races with a putenv
+// from another thread), one rule for all five.  A search reads them once, into its plan (knn_options, plan_search).
 std::atomic<int> g_knn_opt[MQ_KNN_OPT_COUNT];
 std::once_flag g_knn_opt_once;
 void knn_opt_init() {
@@ -75,12 +77,24 @@ constexpr int LDS_XS = 0;                                   // [NSTAGE][4][16][6
 constexpr int LDS_QS = LDS_XS + NSTAGE * 4 * BK * 64 * 4;   // [NSTAGE][4][16][64] f32
 constexpr int LDS_CNT = LDS_QS + NSTAGE * 4 * BK * 64 * 4;  // gcnt[256] int, tau[256] f32
 constexpr int LDS_TOTAL = LDS_CNT + 2 * TQ * 4;
-constexpr int KF = MQ_KNN_FUSED_K;  // neighbours one fused scan keeps; a larger k runs ceil(k / KF) rounds (see knn_search_impl)
+constexpr int KF = MQ_KNN_FUSED_K;  // neighbours one fused scan keeps; a larger k runs ceil(k / KF) rounds (see exact_scan_rounds)
 // neighbours the screened search serves itself (final_select sorts up to 256 exact keys).  Measured at 1.5M x 768, 4096 queries:
 // k = 129 / 200 / 224 / 240: 8.8 / 9.8 / 10.2 / 11.1 ms; from k = 248 the stripe bound (256 slots per query) no longer yields a
 // threshold, the slab pools overflow and every tile falls back to the exact rounds (160-176 ms against 146 for the rounds alone).
 constexpr int SCREEN_MAX_K = 224;
 constexpr int FINAL_SORT_KEYS = 256;
+// ---- k beyond the screen's own range (SCREEN_MAX_K) ------------------------------------------------------------------------
+// The screen's bounded buffers serve k <= 224 (256 stripe maxima per query, 256 keys in the final sort).  A larger k is served by
+// PARTITIONS: the rows are cut into P contiguous ranges, each range is searched for its exact top-224 by the screened pipeline, the
+// P lists are merged, and the merge PROVES the result: the top-k of the union is the top-k of the lists unless some range delivered
+// its whole list into it (it might have held a 225th) -- then that query tile is recomputed by the exact rounds, like a tile whose
+// screening buffers overflowed.  P = ceil(k / 112): on exchangeable data a range holds ~k / P <= 112 of the top k, half of what it
+// can deliver; a KB sorted by similarity to the query defeats it and pays the exact rounds for those tiles.  Cost: one pass of the
+// scan over all rows + P tails, instead of ceil(k / 128) exact fp32 scans (k = 256 at 1.5M x 768, 4096 queries: 146 ms).
+constexpr int PART_K = SCREEN_MAX_K;       // neighbours asked of each range
+constexpr int PART_SHARE = 112;            // expected neighbours per range at most
+constexpr int PART_MAX = 16;               // ranges at most: k <= 1792
+constexpr int PART_MIN_ROWS = 16384;       // ranges smaller than this: the exact rounds are as fast
 static_assert(KF + TN <= POOL, "a compacted pool must take every row of one more chunk");
 static_assert(KF == 128, "sort128_desc / the merge kernels are written for 128-entry lists");
 
@@ -978,9 +992,73 @@ __global__ __launch_bounds__(256) void shard_merge_big_kernel(const float* __res
 #include "knn_small8.inc"
 #include "knn_direct.inc"
 
+}  // namespace
+
+// One workgroup per query: the P lists (PART_K entries each, best first) -> the k best of their union, best first, and the proof
+// obligation: a range all of whose PART_K entries are inside the answer (and which holds more rows than that) flags the query's tile.
+// (C linkage: the plain name this kernel has always had in traces and profiles.)
+extern "C" __global__ __launch_bounds__(256) void partition_merge_kernel(const float* __restrict__ Dp, const long long* __restrict__ Ip, int P, int nq,
+                                                              int k, int l2, unsigned flip, long long id_offset, long long per,
+                                                              long long N, float* __restrict__ D, long long* __restrict__ I,
+                                                              int* __restrict__ flags) {
+    __shared__ u64 keys[PART_MAX * 256];
+    __shared__ int cnt[PART_MAX];
+    const int q = blockIdx.x, t = threadIdx.x;
+    const int total = P * PART_K;
+    int n2 = 256;
+    while (n2 < total) n2 <<= 1;
+    if (t < PART_MAX) cnt[t] = 0;
+    for (int e = t; e < n2; e += 256) {
+        u64 key = 0ull;
+        if (e < total) {
+            const int p = e / PART_K, j = e - p * PART_K;
+            const size_t at = ((size_t)p * nq + q) * PART_K + j;
+            const long long id = Ip[at];
+            if (id >= 0) {
+                const float sc = Dp[at];
+                key = make_key(l2 ? -sc : sc, (unsigned)id ^ flip);
+            }
+        }
+        keys[e] = key;
+    }
+    __syncthreads();
+    // bitonic sort, descending
+    for (int sz = 2; sz <= n2; sz <<= 1)
+        for (int j = sz >> 1; j > 0; j >>= 1) {
+            for (int e = t; e < n2 / 2; e += 256) {
+                const int lo = ((e & ~(j - 1)) << 1) | (e & (j - 1)), hi = lo | j;
+                const bool desc = (lo & sz) == 0;
+                const u64 x = keys[lo], y = keys[hi];
+                if ((x < y) == desc) { keys[lo] = y; keys[hi] = x; }
+            }
+            __syncthreads();
+        }
+    for (int e = t; e < k; e += 256) {
+        const u64 key = keys[e];
+        float sc = l2 ? FLT_MAX : -FLT_MAX;  // FAISS's heap neutral values in unfilled slots
+        long long id = -1;
+        if (key) {
+            const unsigned row = key_row(key) ^ flip;
+            const float g = key_score(key);
+            sc = l2 ? -g : g;
+            id = (long long)row + id_offset;
+            atomicAdd(&cnt[(int)(row / (unsigned long long)per)], 1);
+        }
+        D[(size_t)q * k + e] = sc;
+        I[(size_t)q * k + e] = id;
+    }
+    __syncthreads();
+    if (t < P) {
+        const long long rows = (t + 1) * per <= N ? per : N - t * per;
+        if (cnt[t] >= PART_K && rows > PART_K) flags[q / TQ] = 1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+namespace {
+
 thread_local int g_last_hip_error = 0;
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
@@ -995,6 +1073,15 @@ inline unsigned long long* dbg_ptr() {
 #else
     return nullptr;
 #endif
+}
+
+// One launch of a kernel that asks for dynamic LDS: raise the kernel's limit (once per device), launch, report.  The kernel is a
+// template argument, so every kernel has its own "already raised" word.
+template <auto KERNEL, typename... Args>
+int launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
+    MQ_DYNAMIC_LDS(lds, KERNEL);
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+    return mq_launch_status();
 }
 
 int num_cus() {
@@ -1093,40 +1180,320 @@ Geometry geometry(int64_t N, int d, int nq, int k, int cus, int metric = -1) {
     return g;
 }
 
+// ---- the plan of one search ------------------------------------------------------------------------------------------------
+// Which way a call is served is decided HERE, once, from (N, d, nq, k, metric) and the A/B switches: the search entries, the
+// workspace-size entries and mq_knn_screen_scan_kind all read the same Plan.
+enum Route {
+    ROUTE_L2_DIRECT,      // metric L2, fewer than MQ_KNN_L2_DIRECT_BELOW queries: FAISS's sequential form (knn_direct.inc)
+    ROUTE_ROW_RANGES,     // SCREEN_MAX_K < k <= 1792: the screen over P contiguous row ranges, merged and proved (PART_*, above)
+    ROUTE_EXACT_ROUNDS,   // ceil(k / KF) rounds of the exact fp32 scan: the exact entry; k beyond the screen (its bounded buffers are
+                          // sized for the reference's k = 100: 512 survivors per slab pool, 256 stripe slots) and no row ranges
+    ROUTE_SCREEN_STREAM,  // the screen, scanned by the streaming kernel for one query tile (knn_small8.inc)
+    ROUTE_SCREEN_TILE,    // the screen, scanned by the 256 x 256 tile kernel
+};
+
+// the A/B switches (mq_knn_set_option), read once per call
+struct KnnOptions { int small_scan, small_min_tiles, partitions, scan_mfma; };
+KnnOptions knn_options() {
+    return {knn_opt(MQ_KNN_OPT_SMALL_SCAN), knn_opt(MQ_KNN_OPT_SMALL_MIN_TILES), knn_opt(MQ_KNN_OPT_PARTITIONS), knn_opt(MQ_KNN_OPT_SCAN_MFMA)};
+}
+
+// P row ranges of `per` rows (P = 0: none), and their scratch behind the plain workspace (g.total): Dp [P][nq][PART_K] f32 |
+// Ip [P][nq][PART_K] i64 | pflags [query tiles] int, at these byte offsets
+struct PartPlan { int P; int64_t per; size_t off_Ip, off_flags, bytes; };
+PartPlan partition_plan(int64_t N, int nq, int k, const KnnOptions& o) {
+    PartPlan pl{0, 0, 0, 0, 0};
+    if (!o.partitions || k <= SCREEN_MAX_K) return pl;
+    const int P = (k + PART_SHARE - 1) / PART_SHARE;
+    if (P > PART_MAX) return pl;
+    const int64_t per = round_up((N + P - 1) / P, TQ);  // the bf16 copy is stored in 256-row tiles
+    if (per < PART_MIN_ROWS || (int64_t)(P - 1) * per >= N) return pl;
+    pl.P = P; pl.per = per;
+    const size_t e = (size_t)P * (size_t)(nq > 0 ? nq : 1) * PART_K;
+    pl.off_Ip = (size_t)round_up((int64_t)(e * 4), 256);
+    pl.off_flags = pl.off_Ip + (size_t)round_up((int64_t)(e * 8), 256);
+    pl.bytes = pl.off_flags + (size_t)round_up((int64_t)((nq + TQ - 1) / TQ + 1) * 4, 256);
+    return pl;
+}
+
+struct Plan {
+    Geometry g;
+    Route route;
+    int dp;            // bf16 row length of the screening copy the call reads (screen_dp)
+    int nkb;           // ROUTE_SCREEN_STREAM: K blocks of queries in registers ...
+    bool rowterm;      // ... and whether the row term sits beside them as fp32 (below)
+    int walk;          // cand_select_kernel's pool walk (CSEL_WALK_*): follows the layout the chosen scan leaves
+    int scan_mfma;     // ROUTE_SCREEN_TILE: MQ_KNN_OPT_SCAN_MFMA of this call
+    PartPlan part;     // the row ranges (N, k) has, whatever the route: their scratch is reserved with the workspace ...
+    size_t ws_report;  // ... that the size entries report: g.total + part.bytes
+    size_t ws_need;    // what THIS route needs: g.total, + part.bytes on ROUTE_ROW_RANGES
+};
+
 // The streaming kernel for one query tile (knn_small8.inc) serves a screened search when its geometry holds: one query tile,
 // one slab per stripe slot (S = 256 = TQ: the workgroup of slab s owns query s), at most 12 K blocks of queries in registers,
 // k within the stripe bound, and enough 32-row tiles per slab for the ring to pay.  MQ_KNN_OPT_SMALL_SCAN = 0 switches it off,
 // MQ_KNN_OPT_SMALL_MIN_TILES = <n> lowers the tiles-per-slab floor (tests) -- mq_knn_set_option.
-// `rowterm` (out): the L2 metric / the centred inner product whose two row-term columns sit alone in a 13th K block (d a multiple of 64, dp = d + 64 = 832):
-// the kernel's ROWTERM instance reads 12 K blocks and takes the term as fp32.
-bool small_scan_serves(const Geometry& g, int64_t N, int d, int metric, int k, int* nkb_out = nullptr, bool* rowterm_out = nullptr) {
-    const int enabled = knn_opt(MQ_KNN_OPT_SMALL_SCAN), floor_opt = knn_opt(MQ_KNN_OPT_SMALL_MIN_TILES);
-    const int min_tiles = floor_opt > 0 ? floor_opt : SM_MIN_TILES_PER_SLAB;
-    if (!enabled || g.nqt != 1 || g.S != TQ || g.ms != SMAX_SLOTS || g.sps != 1) return false;
-    int nkb = screen_dp(d, metric) / SBK;
+// `rowterm`: the L2 metric / the centred inner product whose two row-term columns sit alone in a 13th K block (d a multiple of 64,
+// dp = d + 64 = 832): the kernel's ROWTERM instance reads 12 K blocks and takes the term as fp32.
+bool stream_scan_serves(Plan& p, int64_t N, int d, int metric, int k, const KnnOptions& o) {
+    const Geometry& g = p.g;
+    const int min_tiles = o.small_min_tiles > 0 ? o.small_min_tiles : SM_MIN_TILES_PER_SLAB;
+    if (!o.small_scan || g.nqt != 1 || g.S != TQ || g.ms != SMAX_SLOTS || g.sps != 1) return false;
+    int nkb = p.dp / SBK;
     bool rowterm = false;
     if (nkb == SM_MAX_NKB + 1 && (metric == MQ_METRIC_L2 || metric == MQ_METRIC_IP_CENTRED) && d % SBK == 0) {
         nkb = SM_MAX_NKB;
         rowterm = true;
     }
     if (nkb > SM_MAX_NKB || k > KF) return false;
-    if (nkb_out) *nkb_out = nkb;
-    if (rowterm_out) *rowterm_out = rowterm;
+    p.nkb = nkb;
+    p.rowterm = rowterm;
     return (N + SM_ROWS - 1) / SM_ROWS >= (int64_t)g.S * (min_tiles > 1 ? min_tiles : 1);
+}
+
+// metric: the code the caller passed (MQ_METRIC_IP_CENTRED included), or -1 = unknown (mq_knn_workspace_bytes: reserve what either
+// metric needs).  screened: the call came through mq_knn_search_screened_f32 (the exact entry knows two routes).
+Plan plan_search(int64_t N, int d, int nq, int k, int metric, const KnnOptions& o, bool screened = true) {
+    Plan p{};
+    p.g = geometry(N, d, nq, k, num_cus(), metric < 0 ? -1 : true_metric(metric));
+    p.dp = screen_dp(d, metric);
+    p.scan_mfma = o.scan_mfma;
+    p.part = partition_plan(N, nq, k, o);
+    if (metric == MQ_METRIC_L2 && nq < MQ_KNN_L2_DIRECT_BELOW) p.route = ROUTE_L2_DIRECT;
+    else if (!screened) p.route = ROUTE_EXACT_ROUNDS;
+    else if (p.part.P) p.route = ROUTE_ROW_RANGES;
+    else if (k > SCREEN_MAX_K) p.route = ROUTE_EXACT_ROUNDS;
+    else p.route = stream_scan_serves(p, N, d, metric, k, o) ? ROUTE_SCREEN_STREAM : ROUTE_SCREEN_TILE;
+    p.walk = p.route == ROUTE_SCREEN_STREAM ? CSEL_WALK_HALVES : (p.g.S >= 64 ? CSEL_WALK_SLICE_LINES : CSEL_WALK_SLICES);
+    p.ws_report = p.g.total + p.part.bytes;
+    p.ws_need = p.g.total + (p.route == ROUTE_ROW_RANGES ? p.part.bytes : 0);
+    return p;
+}
+
+// ---- the workspace as typed pointers: THE carve of what geometry() and partition_plan() lay out ---------------------------
+struct Workspace {
+    char* base;
+    float *Qp, *qn;        // fp32 query panels, ||q||^2
+    float* qtmp;           // row-major queries after the "L2norm," transform
+    u64* lists;            // the exact scan's lists = the screen's pools = the direct form's segment winners
+    unsigned short* Qb;    // bf16 queries
+    float* margin;
+    int *pcount, *ovf;
+    unsigned *gthr, *smax;
+    unsigned* cand;
+    u64* ckeys;
+    int* ccount;
+    u64* ceil;             // per-query key ceilings of a search for more than KF neighbours
+    float *dqt, *ddist;    // direct form: transposed queries, distance matrix
+    float* Dp;             // row ranges (behind g.total): the ranges' lists and the flags of the merge
+    long long* Ip;
+    int* pflags;
+};
+Workspace workspace_view(const Plan& p, void* ws_dev) {
+    const Geometry& g = p.g;
+    char* ws = (char*)ws_dev;
+    Workspace w;
+    w.base = ws;
+    w.Qp = (float*)(ws + g.off_qp);
+    w.qn = (float*)(ws + g.off_qn);
+    w.qtmp = (float*)(ws + g.off_qtmp);
+    w.lists = (u64*)(ws + g.off_lists);
+    w.Qb = (unsigned short*)(ws + g.off_qb);
+    w.margin = (float*)(ws + g.off_margin);
+    w.pcount = (int*)(ws + g.off_pcount);
+    w.ovf = (int*)(ws + g.off_ovf);
+    w.gthr = (unsigned*)(ws + g.off_gthr);
+    w.smax = (unsigned*)(ws + g.off_smax);
+    w.cand = (unsigned*)(ws + g.off_cand);
+    w.ckeys = (u64*)(ws + g.off_ckeys);
+    w.ccount = (int*)(ws + g.off_ccount);
+    w.ceil = (u64*)(ws + g.off_ceil);
+    w.dqt = (float*)(ws + g.off_dqt);
+    w.ddist = (float*)(ws + g.off_ddist);
+    w.Dp = (float*)(ws + g.total);
+    w.Ip = (long long*)(ws + g.total + p.part.off_Ip);
+    w.pflags = (int*)(ws + g.total + p.part.off_flags);
+    return w;
+}
+
+// ---- one search call ---------------------------------------------------------------------------------------------------------
+// The arguments of the search entries.  The exact entry leaves rowmajor / bf16 / xstats null; a screened index that keeps no
+// panel copy leaves packed null: the exact scan and the direct form then read the row-major copy.
+struct SearchCall {
+    const float *packed, *sqnorm, *rowmajor;
+    const uint16_t* bf16;
+    const float* xstats;
+    int64_t N;
+    int d;
+    const float* queries;
+    int nq, k, metric, flags;
+    int64_t id_offset;
+    float* D;
+    int64_t* I;
+    hipStream_t st;
+    void *ev0, *ev1;              // optional hipEvent_t recorded around the call's scan
+    unsigned long long* scan_dbg; // MQ_TIMING builds: the timestamp buffer of the exact entry's scan
+};
+
+// "L2norm," arithmetic of a call's query transform: 0 = none, MQ_L2NORM_NUMPY, MQ_L2NORM_FAISS (the flag alone means FAISS form too)
+inline int query_l2norm_form(int flags) {
+    if (flags & MQ_KNN_FLAG_L2NORM_FAISS) return MQ_L2NORM_FAISS;
+    return (flags & MQ_KNN_FLAG_L2NORM_QUERIES) ? MQ_L2NORM_NUMPY : 0;
+}
+constexpr int MQ_KNN_ALL_FLAGS = MQ_KNN_FLAG_L2NORM_QUERIES | MQ_KNN_FLAG_TIE_ID_DESC | MQ_KNN_FLAG_L2NORM_FAISS;
+constexpr int MQ_KNN_SCREENED_FLAGS = MQ_KNN_ALL_FLAGS | MQ_KNN_FLAG_PHASE_FRONT | MQ_KNN_FLAG_PHASE_TAIL;
+
+// tie order of a call: key low word = ~(row ^ flip)
+inline unsigned tie_flip(int flags) { return (flags & MQ_KNN_FLAG_TIE_ID_DESC) ? 0xFFFFFFFFu : 0u; }
+
+// rounds of a search: ceil(k / KF) fused selections of up to KF neighbours each; round r > 0 only admits keys strictly below
+// the last key of round r - 1 (keys are unique, so the rounds' results concatenate into the exact sorted top-k)
+inline int n_rounds(int k) { return (k + KF - 1) / KF; }
+
+// THE argument check of the search entries (after their `nq == 0 -> MQ_OK`), and the plan of an admitted call.  Precedence:
+// MQ_EINVAL, MQ_EUNSUPPORTED, MQ_EWORKSPACE.  The exact entry takes an empty shard (N = 0: every slot unfilled), the screened
+// one does not.
+int admit_search(const SearchCall& c, bool screened, const void* ws_dev, size_t ws_bytes, const KnnOptions& o, Plan* plan) {
+    const bool pointers = c.sqnorm && c.queries && c.D && c.I && ws_dev && (screened ? c.rowmajor && c.bf16 && c.xstats : c.packed != nullptr);
+    const bool metric_ok = screened ? screen_metric_ok(c.metric) : (c.metric == MQ_METRIC_IP || c.metric == MQ_METRIC_L2);
+    if (!pointers || !metric_ok || (c.flags & ~(screened ? MQ_KNN_SCREENED_FLAGS : MQ_KNN_ALL_FLAGS))) return MQ_EINVAL;
+    if (c.N < (screened ? 1 : 0) || c.d <= 0 || c.nq < 0 || c.k <= 0) return MQ_EINVAL;
+    if (c.k > MQ_KNN_MAX_K) return MQ_EUNSUPPORTED;
+    if (c.N >= 0xFFFFFFFFll) return MQ_EUNSUPPORTED;  // 32-bit local row ids
+    *plan = plan_search(c.N, c.d, c.nq, c.k, c.metric, o, screened);
+    return ws_bytes < plan->ws_need ? MQ_EWORKSPACE : MQ_OK;
+}
+
+// ---- stages ------------------------------------------------------------------------------------------------------------------
+// The queries in row-major form after the optional "L2norm," transform, applied ONCE (so that the panel copy, the bf16 copy, the
+// re-scoring and the direct form all see the same fp32 values).  run = false (a TAIL call): only name what the FRONT call made.
+int prepare_queries(const SearchCall& c, const Workspace& w, bool run, const float** q_rm) {
+    const int form = query_l2norm_form(c.flags);
+    *q_rm = form ? w.qtmp : c.queries;
+    if (!form || !run) return MQ_OK;
+    MQ_HIP(hipMemcpyAsync(w.qtmp, c.queries, (size_t)c.nq * c.d * 4, hipMemcpyDeviceToDevice, c.st));
+    launch_l2norm_rows(w.qtmp, (int64_t)c.nq, c.d, form, c.st);
+    return mq_launch_status();
+}
+
+// queries -> fp32 panel layout (+ the optional "L2norm," transform `form`, + ||q||^2) for the exact scan.  `only`: the flagged
+// query tiles alone.  `clear`: panels and norms are zeroed first and the pack covers the real queries; without it every panel of
+// the padded tiles is written, padding rows included (the screened tail: panels of flagged tiles only, no clearing launch in front).
+int pack_query_panels(const SearchCall& c, const Plan& p, const Workspace& w, const float* q, int form, const int* only, bool clear) {
+    const Geometry& g = p.g;
+    if (clear) MQ_HIP(hipMemsetAsync(w.Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, c.st));
+    const unsigned panels = clear ? (unsigned)((c.nq + PANEL - 1) / PANEL) : (unsigned)(g.nqpad / PANEL);
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(panels), dim3(256), 0, c.st, q, (int64_t)c.nq, c.d, g.dpad, (int64_t)0, form, w.Qp, w.qn,
+                       only, clear ? (int64_t)0 : (int64_t)g.nqpad);
+    return mq_launch_status();
+}
+
+// launch of one exact scan (8 instantiations: metric x operand layout x key ceiling)
+template <int METRIC>
+int launch_scan_m(bool xrow, bool ceil, const ScanArgs& a, hipStream_t st) {
+    const dim3 grid((unsigned)(a.nqt * a.S)), block(1024);
+    if (!xrow && !ceil) return launch_lds<knn_scan_kernel<METRIC, false, false>>(grid, block, LDS_TOTAL, st, a);
+    if (xrow && !ceil) return launch_lds<knn_scan_kernel<METRIC, true, false>>(grid, block, LDS_TOTAL, st, a);
+    if (!xrow) return launch_lds<knn_scan_kernel<METRIC, false, true>>(grid, block, LDS_TOTAL, st, a);
+    return launch_lds<knn_scan_kernel<METRIC, true, true>>(grid, block, LDS_TOTAL, st, a);
+}
+
+// per-query merge of the slabs' lists of one round into columns [col0, col0 + k) of D, I
+int launch_slab_merge(const SearchCall& c, const Plan& p, const Workspace& w, int k, const int* only, int col0, u64* next_ceil) {
+    const auto merge = true_metric(c.metric) == MQ_METRIC_IP ? slab_merge_kernel<MQ_METRIC_IP> : slab_merge_kernel<MQ_METRIC_L2>;
+    hipLaunchKernelGGL(merge, dim3((unsigned)c.nq), dim3(128), 0, c.st, w.lists, c.nq, p.g.S, k, (long long)c.id_offset, c.D,
+                       (long long*)c.I, only, tie_flip(c.flags), c.k, col0, next_ceil);
+    return mq_launch_status();
+}
+
+// The exact scan over a shard whose query panels (w.Qp, w.qn) are ready: one fused scan + slab merge per round of KF neighbours
+// (ONE round for k <= 128, the reference's k = 100), from the panel copy or, without one, from the row-major copy.  `only`: the
+// flagged query tiles alone.  ev0 / ev1: optional events around the first round's scan.
+int exact_scan_rounds(const SearchCall& c, const Plan& p, const Workspace& w, const int* only, void* ev0, void* ev1) {
+    const Geometry& g = p.g;
+    const bool xrow = c.packed == nullptr;
+    ScanArgs a;
+    a.Xp = xrow ? c.rowmajor : c.packed; a.Qp = w.Qp; a.xn = c.sqnorm; a.qn = w.qn; a.lists = w.lists; a.d = c.d;
+    a.N = c.N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = c.scan_dbg; a.only = only;
+    a.flip = tie_flip(c.flags);
+    const int R = n_rounds(c.k);
+    for (int r = 0; r < R; ++r) {
+        const int kr = c.k - r * KF < KF ? c.k - r * KF : KF;
+        a.k = kr;
+        a.ceil = r ? w.ceil : nullptr;
+        if (r == 0 && ev0) MQ_HIP(hipEventRecord((hipEvent_t)ev0, c.st));
+        const int rc = true_metric(c.metric) == MQ_METRIC_L2 ? launch_scan_m<MQ_METRIC_L2>(xrow, r > 0, a, c.st)
+                                                             : launch_scan_m<MQ_METRIC_IP>(xrow, r > 0, a, c.st);
+        if (rc != MQ_OK) return rc;
+        if (r == 0 && ev1) MQ_HIP(hipEventRecord((hipEvent_t)ev1, c.st));
+        const int rm = launch_slab_merge(c, p, w, kr, only, r * KF, r + 1 < R ? w.ceil : (u64*)nullptr);
+        if (rm != MQ_OK) return rm;
+    }
+    return MQ_OK;
+}
+
+// THE fallback of the screened entry: the fp32 panels of the row-major queries `q_rm`, then the exact rounds -- for every query
+// tile (only = null), or for the tiles a stage flagged (a no-op otherwise: every workgroup of an unflagged tile returns at once).
+enum Panels { PANELS_READY, PANELS_PACK, PANELS_CLEAR_AND_PACK };  // READY: made in front of the screen (L2: the re-scoring needs ||q||^2)
+int exact_fallback(const SearchCall& c, const Plan& p, const Workspace& w, const float* q_rm, const int* only, Panels panels,
+                   void* ev0 = nullptr, void* ev1 = nullptr) {
+    if (panels != PANELS_READY)
+        if (const int rc = pack_query_panels(c, p, w, q_rm, 0, only, panels == PANELS_CLEAR_AND_PACK); rc != MQ_OK) return rc;
+    return exact_scan_rounds(c, p, w, only, ev0, ev1);
+}
+
+// ROUTE_EXACT_ROUNDS of the exact entry: the "L2norm," transform rides in the panel pack; an empty shard leaves every slot unfilled
+int search_exact(const SearchCall& c, const Plan& p, const Workspace& w) {
+    // queries -> panel layout; padded queries are zero
+    if (const int rc = pack_query_panels(c, p, w, c.queries, query_l2norm_form(c.flags), nullptr, true); rc != MQ_OK) return rc;
+    if (c.N > 0) return exact_scan_rounds(c, p, w, nullptr, c.ev0, c.ev1);
+    MQ_HIP(hipMemsetAsync(w.lists, 0, (size_t)p.g.nqt * p.g.S * TQ * (size_t)POOL * 8, c.st));
+    for (int r = 0; r < n_rounds(c.k); ++r) {
+        const int kr = c.k - r * KF < KF ? c.k - r * KF : KF;
+        if (const int rm = launch_slab_merge(c, p, w, kr, nullptr, r * KF, nullptr); rm != MQ_OK) return rm;
+    }
+    return MQ_OK;
+}
+
+// ROUTE_L2_DIRECT: FAISS's sequential path, d = sum_k (q[k] - x[k])^2 (knn_direct.inc), over the panel copy or the row-major one
+int search_l2_direct(const SearchCall& c, const Plan& p, const Workspace& w, const float* q_rm) {
+    const Geometry& g = p.g;
+    const hipStream_t st = c.st;
+    const unsigned flip = tie_flip(c.flags);
+    const long long N = (long long)c.N;
+    hipLaunchKernelGGL(direct_transpose_queries_kernel, dim3((unsigned)((g.dpad * DIRECT_NQ + 255) / 256)), dim3(256), 0, st, q_rm,
+                       c.nq, c.d, g.dpad, w.dqt);
+    MQ_HIP(hipGetLastError());
+    const long long seg = (long long)((g.nchunks + g.S - 1) / g.S) * TN;  // rows per selection segment
+    if (N > 0) {
+        if (c.packed)
+            hipLaunchKernelGGL(l2_direct_dist_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c.packed, w.dqt, N, c.d, g.dpad,
+                               c.nq, (long long)g.npad, w.ddist);
+        else
+            hipLaunchKernelGGL(l2_direct_dist_rows_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c.rowmajor, w.dqt, N, c.d,
+                               c.nq, (long long)g.npad, w.ddist);
+        MQ_HIP(hipGetLastError());
+    }
+    const int R = n_rounds(c.k);
+    for (int r = 0; r < R; ++r) {
+        const int kr = c.k - r * KF < KF ? c.k - r * KF : KF;
+        // segment winners live in the (much larger) pool region of the other paths: nq * S * 128 keys
+        hipLaunchKernelGGL(l2_direct_select_kernel, dim3((unsigned)g.S, (unsigned)c.nq), dim3(256), 0, st, w.ddist, N, (long long)g.npad,
+                           seg, kr, w.lists, flip, r ? (const u64*)w.ceil : (const u64*)nullptr);
+        MQ_HIP(hipGetLastError());
+        hipLaunchKernelGGL(l2_direct_final_kernel, dim3((unsigned)c.nq), dim3(256), 0, st, w.lists, g.S, kr, (long long)c.id_offset, c.D,
+                           (long long*)c.I, flip, c.k, r * KF, r + 1 < R ? w.ceil : (u64*)nullptr);
+        MQ_HIP(hipGetLastError());
+    }
+    return MQ_OK;
 }
 
 template <int NKB>
 int launch_small_scan_n(const SmallArgs& sa, int S, hipStream_t st) {
     constexpr int lds = sm_nst(NKB) * (NKB * SM_PIECE + 2 * SM_AUX) + 2 * TQ * 4 + SM_AUX;
-    if (NKB == SM_MAX_NKB && sa.rowterm) {  // the row term as fp32 beside 12 K blocks
-        constexpr int lds_rt = lds + sm_nst(SM_MAX_NKB) * SM_AUX;  // + the ring slots' row terms
-        MQ_DYNAMIC_LDS(lds_rt, screen_small8_kernel<SM_MAX_NKB, true>);
-        hipLaunchKernelGGL((screen_small8_kernel<SM_MAX_NKB, true>), dim3((unsigned)S), dim3(512), lds_rt, st, sa);
-        return MQ_OK;
-    }
-    MQ_DYNAMIC_LDS(lds, screen_small8_kernel<NKB>);
-    hipLaunchKernelGGL(screen_small8_kernel<NKB>, dim3((unsigned)S), dim3(512), lds, st, sa);
-    return MQ_OK;
+    if (NKB == SM_MAX_NKB && sa.rowterm)  // the row term as fp32 beside 12 K blocks: + the ring slots' row terms
+        return launch_lds<screen_small8_kernel<SM_MAX_NKB, true>>(dim3((unsigned)S), dim3(512), lds + sm_nst(SM_MAX_NKB) * SM_AUX, st, sa);
+    return launch_lds<screen_small8_kernel<NKB>>(dim3((unsigned)S), dim3(512), lds, st, sa);
 }
 
 int launch_small_scan(const SmallArgs& sa, int nkb, int S, hipStream_t st) {
@@ -1145,6 +1512,152 @@ int launch_small_scan(const SmallArgs& sa, int nkb, int S, hipStream_t st) {
         case 12: return launch_small_scan_n<12>(sa, S, st);
         default: return MQ_EUNSUPPORTED;
     }
+}
+
+// The front of the screen (ROUTE_SCREEN_*): the fp32 panels the L2 metric needs, the bf16 queries, the margin, the scan.
+// MQ_METRIC_IP_CENTRED: the index was built for the centred-query screen (two extra columns = the row term c . (x - c), the
+// centre itself behind the statistics: xstats[4 .. 4 + d)); everything exact -- re-scoring, fallback scans, merges -- is the
+// plain inner product.
+int screen_front(const SearchCall& c, const Plan& p, const Workspace& w, const float* q_rm) {
+    const Geometry& g = p.g;
+    const hipStream_t st = c.st;
+    const int l2 = c.metric == MQ_METRIC_L2, ipc = c.metric == MQ_METRIC_IP_CENTRED, dp = p.dp, nq = c.nq;
+    // The fp32 panel copy of the queries (+ ||q||^2) serves the exact-scan fallback -- and, for the L2 metric, the
+    // re-scoring (||q||^2).  With the inner product it is made after the screened pipeline, for flagged tiles only.
+    if (l2)
+        if (const int rc = pack_query_panels(c, p, w, q_rm, 0, nullptr, true); rc != MQ_OK) return rc;
+    if (g.nqpad > nq)  // bf16 rows of the padding queries: the last tile (tile layout: its real rows are written below)
+        MQ_HIP(hipMemsetAsync(w.Qb + (size_t)(g.nqpad - TQ) * dp, 0, (size_t)TQ * dp * 2, st));
+    const float* centre = ipc ? c.xstats + 4 : (const float*)nullptr;
+    const int64_t quads = (int64_t)nq * (dp / 4);
+    hipLaunchKernelGGL(to_bf16_rows_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, q_rm, (int64_t)nq, c.d, dp, w.Qb,
+                       (l2 || ipc) ? 2 : 0, (const float*)nullptr, centre, (int64_t)0);
+    MQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_margin_kernel, dim3((unsigned)((g.nqpad + 3) / 4)), dim3(256), 0, st, q_rm, w.Qb, c.xstats, nq, (int)g.nqpad,
+                       c.d, dp, w.margin, l2 ? 1 : (ipc ? 2 : 0), centre, (unsigned*)w.ovf,
+                       (g.off_smax + (size_t)g.nqpad * g.ms * 4 - g.off_ovf) / 4);  // clears ovf + gthr + smax
+    MQ_HIP(hipGetLastError());
+    // the bf16 screening scan
+    ScreenArgs a;
+    a.Xb = c.bf16; a.Qb = w.Qb; a.margin = w.margin; a.pools = w.lists; a.pcount = w.pcount; a.ovf = w.ovf; a.gthr = w.gthr;
+    a.smax = w.smax; a.ms = g.ms; a.sps = g.sps;
+    a.dbg = dbg_ptr();
+    a.N = c.N; a.dp = dp; a.nqt = g.nqt; a.S = g.S; a.k = c.k; a.qpx = g.qpx_screen; a.nchunks = g.nchunks;
+    if (c.ev0) MQ_HIP(hipEventRecord((hipEvent_t)c.ev0, st));
+    int rc;
+    if (p.route == ROUTE_SCREEN_STREAM) {  // one query tile: the streaming kernel with the queries in registers (knn_small8.inc)
+        SmallArgs sa;
+        sa.s = a;
+        sa.ntiles = (c.N + SM_ROWS - 1) / SM_ROWS;
+        sa.rowterm = p.rowterm ? 1 : 0;
+        sa.sqn = (p.rowterm && l2) ? c.sqnorm : nullptr;
+        sa.nkb_copy = dp / SBK;
+        rc = launch_small_scan(sa, p.nkb, g.S, st);
+    } else if (p.scan_mfma) {  // the tile kernel on 16x16x32 MFMAs
+        rc = launch_lds<screen_scan16_kernel>(dim3((unsigned)(g.nqt * g.S)), dim3(1024), S_LDS_TOTAL, st, a);
+    } else {  // ... on 32x32x16 MFMAs
+        rc = launch_lds<screen_scan_kernel>(dim3((unsigned)(g.nqt * g.S)), dim3(1024), S_LDS_TOTAL, st, a);
+    }
+    if (rc != MQ_OK) return rc;
+    if (c.ev1) MQ_HIP(hipEventRecord((hipEvent_t)c.ev1, st));
+    return MQ_OK;
+}
+
+// The tail of the screen: candidates -> exact scores -> exact top-k, then the query tiles whose bounded buffers overflowed are
+// recomputed by the exact scan.
+int screen_tail(const SearchCall& c, const Plan& p, const Workspace& w, const float* q_rm) {
+    const Geometry& g = p.g;
+    const hipStream_t st = c.st;
+    const int l2 = c.metric == MQ_METRIC_L2, nq = c.nq, k = c.k;
+    const unsigned flip = tie_flip(c.flags);
+#ifdef MQ_TIMING
+    {
+        unsigned long long* dbg = dbg_ptr();
+        MQ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_cs_dbg), &dbg, sizeof(dbg)));
+    }
+#endif
+    // (the walk is checked against the layout word the scan left)
+    const int* layout_word = g.nqt == 1 ? (const int*)(w.ovf + 1) : (const int*)nullptr;
+    const auto csel = p.walk == CSEL_WALK_HALVES ? cand_select_kernel<CSEL_WALK_HALVES>
+                      : p.walk == CSEL_WALK_SLICE_LINES ? cand_select_kernel<CSEL_WALK_SLICE_LINES> : cand_select_kernel<CSEL_WALK_SLICES>;
+    hipLaunchKernelGGL(csel, dim3((unsigned)nq), dim3(256), 0, st, w.lists, w.pcount, w.margin, (const unsigned*)w.gthr,
+                       (const unsigned*)w.smax, g.ms, w.ovf, nq, g.S, k, w.cand, w.ccount, layout_word);
+    MQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)nq, RMAX / 64), dim3(256), 0, st, c.rowmajor, q_rm, c.d, w.cand, w.ccount, w.ckeys,
+                       l2 ? (const float*)w.qn : (const float*)nullptr, c.sqnorm, flip);
+    MQ_HIP(hipGetLastError());
+    const auto fsel = k <= KF ? final_select_kernel<128> : final_select_kernel<FINAL_SORT_KEYS>;
+    hipLaunchKernelGGL(fsel, dim3((unsigned)nq), dim3(64), 0, st, w.ckeys, w.ccount, w.ovf, k, (long long)c.id_offset, c.D,
+                       (long long*)c.I, l2, flip);
+    MQ_HIP(hipGetLastError());
+    return exact_fallback(c, p, w, q_rm, w.ovf, l2 ? PANELS_READY : PANELS_PACK);
+}
+
+// ROUTE_ROW_RANGES: P contiguous row ranges, each searched for its exact top-PART_K by the screened pipeline in the same
+// workspace, then merged and proved (partition_merge_kernel); flagged query tiles are recomputed by the exact rounds.
+int search_row_ranges(const SearchCall& c, const Plan& p, const Workspace& w, const KnnOptions& o, const float* q_rm) {
+    const PartPlan& pl = p.part;
+    SearchCall r = c;  // one range: no panel copy at its rows, its own lists
+    r.packed = nullptr;
+    r.k = PART_K;
+    for (int i = 0; i < pl.P; ++i) {
+        const int64_t r0 = (int64_t)i * pl.per;
+        r.N = r0 + pl.per <= c.N ? pl.per : c.N - r0;
+        r.sqnorm = c.sqnorm + r0;
+        r.rowmajor = c.rowmajor + (size_t)r0 * c.d;
+        r.bf16 = c.bf16 + (size_t)r0 * p.dp;
+        r.id_offset = r0;
+        r.D = w.Dp + (size_t)i * c.nq * PART_K;
+        r.I = (int64_t*)w.Ip + (size_t)i * c.nq * PART_K;
+        r.ev0 = i == 0 ? c.ev0 : nullptr;
+        r.ev1 = i == pl.P - 1 ? c.ev1 : nullptr;
+        const Plan rp = plan_search(r.N, r.d, r.nq, r.k, r.metric, o);
+        if (rp.g.total > p.g.total) return MQ_EWORKSPACE;
+        const Workspace rw = workspace_view(rp, w.base);
+        if (const int rc = screen_front(r, rp, rw, q_rm); rc != MQ_OK) return rc;
+        if (const int rc = screen_tail(r, rp, rw, q_rm); rc != MQ_OK) return rc;
+    }
+    MQ_HIP(hipMemsetAsync(w.pflags, 0, (size_t)p.g.nqt * 4, c.st));
+    hipLaunchKernelGGL(partition_merge_kernel, dim3((unsigned)c.nq), dim3(256), 0, c.st, w.Dp, w.Ip, pl.P, c.nq, c.k,
+                       c.metric == MQ_METRIC_L2 ? 1 : 0, tie_flip(c.flags), (long long)c.id_offset, (long long)pl.per, (long long)c.N, c.D,
+                       (long long*)c.I, w.pflags);
+    MQ_HIP(hipGetLastError());
+    return exact_fallback(c, p, w, q_rm, w.pflags, PANELS_CLEAR_AND_PACK);
+}
+
+// bf16 screening copy + error statistics of rows [row_offset, row_offset + n) of the row-major store
+int screen_copy_and_stats(const float* sqnorm_dev, int d, int metric, int64_t row_offset, int64_t n, float* rowmajor_dev,
+                          uint16_t* bf16_dev, float* xstats_dev, const float* center_dev, hipStream_t st) {
+    const int dp = screen_dp(d, metric);
+    const float* rm = rowmajor_dev + (size_t)row_offset * d;
+    const int64_t quads = n * (int64_t)(dp / 4);
+    if (metric == MQ_METRIC_IP_CENTRED)  // rows of x - c and their row term c . (x - c): 64 rows per workgroup
+        hipLaunchKernelGGL(to_bf16_rows_centred_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, rm, n, d, dp,
+                           (unsigned short*)bf16_dev, center_dev, row_offset);
+    else
+        hipLaunchKernelGGL(to_bf16_rows_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, rm, n, d, dp,
+                           (unsigned short*)bf16_dev, metric == MQ_METRIC_L2 ? 1 : 0, sqnorm_dev + row_offset, center_dev, row_offset);
+    MQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(row_err_stats_kernel, dim3((unsigned)((n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048)), dim3(256), 0, st, rm,
+                       (const unsigned short*)bf16_dev, n, d, dp, (unsigned*)xstats_dev, center_dev, row_offset,
+                       metric == MQ_METRIC_L2 ? 1 : 0);
+    return mq_launch_status();
+}
+
+int topk_merge_impl(const float* Ds_dev, const int64_t* Is_dev, size_t d_stride, size_t i_stride, int nshards, int nq,
+                    int k, int metric_and_tie, float* D_dev, int64_t* I_dev, void* stream) {
+    if (nq == 0) return MQ_OK;
+    if (!Ds_dev || !Is_dev || !D_dev || !I_dev || nshards <= 0 || nq < 0 || k <= 0) return MQ_EINVAL;
+    const bool desc = (metric_and_tie & MQ_MERGE_TIE_ID_DESC) != 0;
+    const int metric = metric_and_tie & ~MQ_MERGE_TIE_ID_DESC;
+    if (metric != MQ_METRIC_IP && metric != MQ_METRIC_L2) return MQ_EINVAL;
+    if (k > MQ_KNN_MAX_K) return MQ_EUNSUPPORTED;
+    const bool ip = metric == MQ_METRIC_IP;
+    const auto merge = k > KF ? (ip ? shard_merge_big_kernel<MQ_METRIC_IP> : shard_merge_big_kernel<MQ_METRIC_L2>)
+                              : (ip ? shard_merge_kernel<MQ_METRIC_IP> : shard_merge_kernel<MQ_METRIC_L2>);
+    hipLaunchKernelGGL(merge, dim3((unsigned)nq), dim3(k > KF ? 256 : 128), 0, (hipStream_t)stream, Ds_dev, (const long long*)Is_dev,
+                       d_stride, i_stride, nshards, nq, k, D_dev, (long long*)I_dev, desc);
+    return mq_launch_status();
 }
 
 }  // namespace
@@ -1216,109 +1729,19 @@ int mq_l2norm_rows_f32(float* rows_dev, int64_t n, int d, void* stream) {
     return mq_l2norm_rows_form_f32(rows_dev, n, d, MQ_L2NORM_NUMPY, stream);
 }
 
-// ---- k beyond the screen's own range (SCREEN_MAX_K) ------------------------------------------------------------------------
-// The screen's bounded buffers serve k <= 224 (256 stripe maxima per query, 256 keys in the final sort).  A larger k is served by
-// PARTITIONS: the rows are cut into P contiguous ranges, each range is searched for its exact top-224 by the screened pipeline, the
-// P lists are merged, and the merge PROVES the result: the top-k of the union is the top-k of the lists unless some range delivered
-// its whole list into it (it might have held a 225th) -- then that query tile is recomputed by the exact rounds, like a tile whose
-// screening buffers overflowed.  P = ceil(k / 112): on exchangeable data a range holds ~k / P <= 112 of the top k, half of what it
-// can deliver; a KB sorted by similarity to the query defeats it and pays the exact rounds for those tiles.  Cost: one pass of the
-// scan over all rows + P tails, instead of ceil(k / 128) exact fp32 scans (k = 256 at 1.5M x 768, 4096 queries: 146 ms).
-constexpr int PART_K = SCREEN_MAX_K;       // neighbours asked of each range
-constexpr int PART_SHARE = 112;            // expected neighbours per range at most
-constexpr int PART_MAX = 16;               // ranges at most: k <= 1792
-constexpr int PART_MIN_ROWS = 16384;       // ranges smaller than this: the exact rounds are as fast
-
-struct PartPlan { int P; int64_t per; };
-static PartPlan partition_plan(int64_t N, int k) {
-    PartPlan pl{0, 0};
-    if (!knn_opt(MQ_KNN_OPT_PARTITIONS) || k <= SCREEN_MAX_K) return pl;
-    const int P = (k + PART_SHARE - 1) / PART_SHARE;
-    if (P > PART_MAX) return pl;
-    const int64_t per = round_up((N + P - 1) / P, TQ);  // the bf16 copy is stored in 256-row tiles
-    if (per < PART_MIN_ROWS || (int64_t)(P - 1) * per >= N) return pl;
-    pl.P = P; pl.per = per;
-    return pl;
-}
-static size_t partition_extra_bytes(int64_t N, int nq, int k) {
-    const PartPlan pl = partition_plan(N, k);
-    if (!pl.P) return 0;
-    const size_t e = (size_t)pl.P * (size_t)(nq > 0 ? nq : 1) * PART_K;
-    return round_up((int64_t)(e * 4), 256) + round_up((int64_t)(e * 8), 256) + round_up((int64_t)((nq + TQ - 1) / TQ + 1) * 4, 256);
-}
-
-// One workgroup per query: the P lists (PART_K entries each, best first) -> the k best of their union, best first, and the proof
-// obligation: a range all of whose PART_K entries are inside the answer (and which holds more rows than that) flags the query's tile.
-__global__ __launch_bounds__(256) void partition_merge_kernel(const float* __restrict__ Dp, const long long* __restrict__ Ip, int P, int nq,
-                                                              int k, int l2, unsigned flip, long long id_offset, long long per,
-                                                              long long N, float* __restrict__ D, long long* __restrict__ I,
-                                                              int* __restrict__ flags) {
-    __shared__ u64 keys[PART_MAX * 256];
-    __shared__ int cnt[PART_MAX];
-    const int q = blockIdx.x, t = threadIdx.x;
-    const int total = P * PART_K;
-    int n2 = 256;
-    while (n2 < total) n2 <<= 1;
-    if (t < PART_MAX) cnt[t] = 0;
-    for (int e = t; e < n2; e += 256) {
-        u64 key = 0ull;
-        if (e < total) {
-            const int p = e / PART_K, j = e - p * PART_K;
-            const size_t at = ((size_t)p * nq + q) * PART_K + j;
-            const long long id = Ip[at];
-            if (id >= 0) {
-                const float sc = Dp[at];
-                key = make_key(l2 ? -sc : sc, (unsigned)id ^ flip);
-            }
-        }
-        keys[e] = key;
-    }
-    __syncthreads();
-    // bitonic sort, descending
-    for (int sz = 2; sz <= n2; sz <<= 1)
-        for (int j = sz >> 1; j > 0; j >>= 1) {
-            for (int e = t; e < n2 / 2; e += 256) {
-                const int lo = ((e & ~(j - 1)) << 1) | (e & (j - 1)), hi = lo | j;
-                const bool desc = (lo & sz) == 0;
-                const u64 x = keys[lo], y = keys[hi];
-                if ((x < y) == desc) { keys[lo] = y; keys[hi] = x; }
-            }
-            __syncthreads();
-        }
-    for (int e = t; e < k; e += 256) {
-        const u64 key = keys[e];
-        float sc = l2 ? FLT_MAX : -FLT_MAX;  // FAISS's heap neutral values in unfilled slots
-        long long id = -1;
-        if (key) {
-            const unsigned row = key_row(key) ^ flip;
-            const float g = key_score(key);
-            sc = l2 ? -g : g;
-            id = (long long)row + id_offset;
-            atomicAdd(&cnt[(int)(row / (unsigned long long)per)], 1);
-        }
-        D[(size_t)q * k + e] = sc;
-        I[(size_t)q * k + e] = id;
-    }
-    __syncthreads();
-    if (t < P) {
-        const long long rows = (t + 1) * per <= N ? per : N - t * per;
-        if (cnt[t] >= PART_K && rows > PART_K) flags[q / TQ] = 1;
-    }
-}
-
 size_t mq_knn_workspace_bytes(int64_t N, int d, int nq, int k) {
     if (N < 0 || d <= 0 || nq < 0 || k <= 0 || k > MQ_KNN_MAX_K) return 0;
-    return geometry(N, d, nq, k, num_cus()).total + partition_extra_bytes(N, nq, k);
+    return plan_search(N, d, nq, k, -1, knn_options()).ws_report;
 }
 
 size_t mq_knn_workspace_bytes_metric(int64_t N, int d, int nq, int k, int metric) {
     if (N < 0 || d <= 0 || nq < 0 || k <= 0 || k > MQ_KNN_MAX_K || !screen_metric_ok(metric)) return 0;
-    return geometry(N, d, nq, k, num_cus(), true_metric(metric)).total + partition_extra_bytes(N, nq, k);
+    return plan_search(N, d, nq, k, metric, knn_options()).ws_report;
 }
 
 int mq_knn_launch_info(int64_t N, int d, int nq, int k, int64_t out[8]) {
     if (!out || N < 0 || d <= 0 || nq < 0 || k <= 0 || k > MQ_KNN_MAX_K) return MQ_EINVAL;
-    const Geometry g = geometry(N, d, nq, k, num_cus());
+    const Geometry g = plan_search(N, d, nq, k, -1, knn_options()).g;
     out[0] = (int64_t)g.nqt * g.S;
     out[1] = 1024;
     out[2] = LDS_TOTAL;
@@ -1333,213 +1756,37 @@ int mq_knn_launch_info(int64_t N, int d, int nq, int k, int64_t out[8]) {
 int mq_knn_screen_scan_kind(int64_t N, int d, int nq, int k, int metric) {
     if (N <= 0 || d <= 0 || nq <= 0 || k <= 0 || k > MQ_KNN_MAX_K) return MQ_EINVAL;
     if (!screen_metric_ok(metric)) return MQ_EINVAL;
-    if (metric == MQ_METRIC_L2 && nq < MQ_KNN_L2_DIRECT_BELOW) return MQ_SCAN_KIND_NONE;
-    if (const PartPlan pl = partition_plan(N, k); pl.P) { N = pl.per; k = PART_K; }  // the scan of each row range
-    if (k > SCREEN_MAX_K) return MQ_SCAN_KIND_NONE;
-    const Geometry g = geometry(N, d, nq, k, num_cus(), true_metric(metric));
-    return small_scan_serves(g, N, d, metric, k) ? MQ_SCAN_KIND_STREAM : MQ_SCAN_KIND_TILE;
-}
-
-// "L2norm," arithmetic of a call's query transform: 0 = none, MQ_L2NORM_NUMPY, MQ_L2NORM_FAISS (the flag alone means FAISS form too)
-static inline int query_l2norm_form(int flags) {
-    if (flags & MQ_KNN_FLAG_L2NORM_FAISS) return MQ_L2NORM_FAISS;
-    return (flags & MQ_KNN_FLAG_L2NORM_QUERIES) ? MQ_L2NORM_NUMPY : 0;
-}
-constexpr int MQ_KNN_ALL_FLAGS = MQ_KNN_FLAG_L2NORM_QUERIES | MQ_KNN_FLAG_TIE_ID_DESC | MQ_KNN_FLAG_L2NORM_FAISS;
-constexpr int MQ_KNN_SCREENED_FLAGS = MQ_KNN_ALL_FLAGS | MQ_KNN_FLAG_PHASE_FRONT | MQ_KNN_FLAG_PHASE_TAIL;
-
-// tie order of a call: key low word = ~(row ^ flip)
-static inline unsigned tie_flip(int flags) { return (flags & MQ_KNN_FLAG_TIE_ID_DESC) ? 0xFFFFFFFFu : 0u; }
-
-// rounds of a search: ceil(k / KF) fused selections of up to KF neighbours each; round r > 0 only admits keys strictly below
-// the last key of round r - 1 (keys are unique, so the rounds' results concatenate into the exact sorted top-k)
-static inline int n_rounds(int k) { return (k + KF - 1) / KF; }
-
-// metric L2 with fewer than 20 queries: FAISS's sequential path, d = sum_k (q[k] - x[k])^2 (knn_direct.inc)
-static int knn_search_l2_direct(const float* packed_dev, const float* rowmajor_dev, int64_t N, int d, const float* queries_dev, int nq, int k,
-                                int flags, int64_t id_offset, float* D_dev, int64_t* I_dev, void* ws_dev,
-                                const Geometry& g, hipStream_t st) {
-    char* ws = (char*)ws_dev;
-    float* qtmp = (float*)(ws + g.off_qtmp);
-    float* Qt = (float*)(ws + g.off_dqt);
-    float* dist = (float*)(ws + g.off_ddist);
-    u64* lists = (u64*)(ws + g.off_lists);
-    u64* ceil = (u64*)(ws + g.off_ceil);
-    const unsigned flip = tie_flip(flags);
-    const float* q_rm = queries_dev;
-    if (query_l2norm_form(flags)) {
-        MQ_HIP(hipMemcpyAsync(qtmp, queries_dev, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, st));
-        launch_l2norm_rows(qtmp, (int64_t)nq, d, query_l2norm_form(flags), st);
-        MQ_HIP(hipGetLastError());
-        q_rm = qtmp;
-    }
-    hipLaunchKernelGGL(direct_transpose_queries_kernel, dim3((unsigned)((g.dpad * DIRECT_NQ + 255) / 256)), dim3(256), 0, st, q_rm,
-                       nq, d, g.dpad, Qt);
-    MQ_HIP(hipGetLastError());
-    const long long seg = (long long)((g.nchunks + g.S - 1) / g.S) * TN;  // rows per selection segment
-    if (N > 0) {
-        if (packed_dev)
-            hipLaunchKernelGGL(l2_direct_dist_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, packed_dev, Qt, (long long)N,
-                               d, g.dpad, nq, (long long)g.npad, dist);
-        else
-            hipLaunchKernelGGL(l2_direct_dist_rows_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, rowmajor_dev, Qt,
-                               (long long)N, d, nq, (long long)g.npad, dist);
-        MQ_HIP(hipGetLastError());
-    }
-    const int R = n_rounds(k);
-    for (int r = 0; r < R; ++r) {
-        const int kr = k - r * KF < KF ? k - r * KF : KF;
-        // segment winners live in the (much larger) pool region of the other paths: nq * S * 128 keys
-        hipLaunchKernelGGL(l2_direct_select_kernel, dim3((unsigned)g.S, (unsigned)nq), dim3(256), 0, st, dist, (long long)N,
-                           (long long)g.npad, seg, kr, lists, flip, r ? (const u64*)ceil : (const u64*)nullptr);
-        MQ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(l2_direct_final_kernel, dim3((unsigned)nq), dim3(256), 0, st, lists, g.S, kr, (long long)id_offset, D_dev,
-                           (long long*)I_dev, flip, k, r * KF, r + 1 < R ? ceil : (u64*)nullptr);
-        MQ_HIP(hipGetLastError());
-    }
-    return MQ_OK;
-}
-
-}  // extern "C"
-// launch of one exact scan (8 instantiations: metric x operand layout x key ceiling)
-template <int METRIC>
-static int launch_scan_m(bool xrow, bool ceil, const ScanArgs& a, hipStream_t st) {
-    const dim3 grid((unsigned)(a.nqt * a.S)), block(1024);
-    if (!xrow && !ceil) { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, false, false>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, false, false>), grid, block, LDS_TOTAL, st, a); }
-    else if (xrow && !ceil) { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, true, false>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, true, false>), grid, block, LDS_TOTAL, st, a); }
-    else if (!xrow) { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, false, true>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, false, true>), grid, block, LDS_TOTAL, st, a); }
-    else { MQ_DYNAMIC_LDS(LDS_TOTAL, knn_scan_kernel<METRIC, true, true>); hipLaunchKernelGGL((knn_scan_kernel<METRIC, true, true>), grid, block, LDS_TOTAL, st, a); }
-    return mq_launch_status();
-}
-static int launch_scan(int metric, bool xrow, bool ceil, const ScanArgs& a, hipStream_t st) {
-    return metric == MQ_METRIC_L2 ? launch_scan_m<MQ_METRIC_L2>(xrow, ceil, a, st) : launch_scan_m<MQ_METRIC_IP>(xrow, ceil, a, st);
-}
-
-// queries -> fp32 panel layout (+ the optional "L2norm," transform `form`, + ||q||^2) for the exact scan.  `only`: the flagged
-// query tiles alone.  `clear`: panels and norms are zeroed first and the pack covers the real queries; without it every panel of
-// the padded tiles is written, padding rows included (the screened tail: panels of flagged tiles only, no clearing launch in front).
-static int pack_query_panels(const Geometry& g, const float* q, int nq, int d, int form, const int* only, bool clear, float* Qp,
-                             float* qn, hipStream_t st) {
-    if (clear) MQ_HIP(hipMemsetAsync(Qp, 0, (size_t)g.nqpad * g.dpad * 4 + (size_t)g.nqpad * 4, st));
-    const unsigned panels = clear ? (unsigned)((nq + PANEL - 1) / PANEL) : (unsigned)(g.nqpad / PANEL);
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(panels), dim3(256), 0, st, q, (int64_t)nq, d, g.dpad, (int64_t)0, form, Qp, qn, only,
-                       clear ? (int64_t)0 : (int64_t)g.nqpad);
-    return mq_launch_status();
-}
-
-// the exact scan's arguments over X (the panel copy, or the row-major copy) for the query panels Qp / qn
-static ScanArgs exact_scan_args(const Geometry& g, const float* X, const float* xn, const float* Qp, const float* qn, u64* lists,
-                                int64_t N, int d, int k, unsigned flip, const int* only, unsigned long long* dbg) {
-    ScanArgs a;
-    a.Xp = X; a.Qp = Qp; a.xn = xn; a.qn = qn; a.lists = lists; a.d = d;
-    a.N = N; a.dpad = g.dpad; a.nqt = g.nqt; a.S = g.S; a.k = k; a.nchunks = g.nchunks; a.qpx = g.qpx; a.dbg = dbg; a.only = only;
-    a.flip = flip; a.ceil = nullptr;
-    return a;
-}
-extern "C" {
-static int launch_slab_merge(int metric, const u64* lists, int nq, int S, int k, int64_t id_offset, float* D_dev, int64_t* I_dev,
-                             const int* only, unsigned flip, int kout, int col0, u64* next_ceil, hipStream_t st) {
-    if (metric == MQ_METRIC_IP)
-        hipLaunchKernelGGL(slab_merge_kernel<MQ_METRIC_IP>, dim3((unsigned)nq), dim3(128), 0, st, lists, nq, S, k, (long long)id_offset,
-                           D_dev, (long long*)I_dev, only, flip, kout, col0, next_ceil);
-    else
-        hipLaunchKernelGGL(slab_merge_kernel<MQ_METRIC_L2>, dim3((unsigned)nq), dim3(128), 0, st, lists, nq, S, k, (long long)id_offset,
-                           D_dev, (long long*)I_dev, only, flip, kout, col0, next_ceil);
-    return mq_launch_status();
-}
-
-// The exact scan over a shard whose query panels (a.Qp, a.qn) are ready: one fused scan + slab merge per round of KF
-// neighbours (ONE round for k <= 128, the reference's k = 100).  a.Xp = the panel copy, or the row-major copy (xrow).
-static int exact_scan_rounds(int metric, bool xrow, ScanArgs a, const Geometry& g, int nq, int k, int64_t id_offset,
-                             float* D_dev, int64_t* I_dev, char* ws, const int* only, hipStream_t st, void* ev0, void* ev1) {
-    u64* ceil = (u64*)(ws + g.off_ceil);
-    const int R = n_rounds(k);
-    for (int r = 0; r < R; ++r) {
-        const int kr = k - r * KF < KF ? k - r * KF : KF;
-        a.k = kr;
-        a.ceil = r ? ceil : nullptr;
-        a.only = only;
-        if (r == 0 && ev0) MQ_HIP(hipEventRecord((hipEvent_t)ev0, st));
-        const int rc = launch_scan(metric, xrow, r > 0, a, st);
-        if (rc != MQ_OK) return rc;
-        if (r == 0 && ev1) MQ_HIP(hipEventRecord((hipEvent_t)ev1, st));
-        const int rm = launch_slab_merge(metric, a.lists, nq, g.S, kr, id_offset, D_dev, I_dev, only, a.flip, k, r * KF,
-                                         r + 1 < R ? ceil : (u64*)nullptr, st);
-        if (rm != MQ_OK) return rm;
-    }
-    return MQ_OK;
-}
-
-static int knn_search_impl(const float* packed_dev, const float* sqnorm_dev, int64_t N, int d, const float* queries_dev,
-                           int nq, int k, int metric, int flags, int64_t id_offset, float* D_dev, int64_t* I_dev,
-                           void* ws_dev, size_t ws_bytes, void* stream, void* ev_scan_begin, void* ev_scan_end) {
-    if (nq == 0) return MQ_OK;
-    if (!packed_dev || !sqnorm_dev || !queries_dev || !D_dev || !I_dev || !ws_dev) return MQ_EINVAL;
-    if (N < 0 || d <= 0 || nq < 0 || k <= 0 || (metric != MQ_METRIC_IP && metric != MQ_METRIC_L2)) return MQ_EINVAL;
-    if (flags & ~MQ_KNN_ALL_FLAGS) return MQ_EINVAL;
-    if (k > MQ_KNN_MAX_K) return MQ_EUNSUPPORTED;
-    if (N >= 0xFFFFFFFFll) return MQ_EUNSUPPORTED;  // 32-bit local row ids
-    const Geometry g = geometry(N, d, nq, k, num_cus(), metric);
-    if (ws_bytes < g.total) return MQ_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)ws_dev;
-    float* Qp = (float*)(ws + g.off_qp);
-    float* qn = (float*)(ws + g.off_qn);
-    u64* lists = (u64*)(ws + g.off_lists);
-    if (metric == MQ_METRIC_L2 && nq < MQ_KNN_L2_DIRECT_BELOW)
-        return knn_search_l2_direct(packed_dev, nullptr, N, d, queries_dev, nq, k, flags, id_offset, D_dev, I_dev, ws_dev, g, st);
-
-    // queries -> panel layout; padded queries are zero
-    if (const int rc = pack_query_panels(g, queries_dev, nq, d, query_l2norm_form(flags), nullptr, true, Qp, qn, st); rc != MQ_OK)
-        return rc;
-    const ScanArgs a = exact_scan_args(g, packed_dev, sqnorm_dev, Qp, qn, lists, N, d, k, tie_flip(flags), nullptr, dbg_ptr());
-    if (N > 0)
-        return exact_scan_rounds(metric, false, a, g, nq, k, id_offset, D_dev, I_dev, ws, nullptr, st, ev_scan_begin, ev_scan_end);
-    MQ_HIP(hipMemsetAsync(lists, 0, (size_t)g.nqt * g.S * TQ * (size_t)POOL * 8, st));
-    for (int r = 0; r < n_rounds(k); ++r) {
-        const int kr = k - r * KF < KF ? k - r * KF : KF;
-        const int rm = launch_slab_merge(metric, lists, nq, g.S, kr, id_offset, D_dev, I_dev, nullptr, a.flip, k, r * KF, nullptr, st);
-        if (rm != MQ_OK) return rm;
-    }
-    return MQ_OK;
-}
-
-int mq_knn_search_f32(const float* packed_dev, const float* sqnorm_dev, int64_t N, int d, const float* queries_dev,
-                      int nq, int k, int metric, int flags, int64_t id_offset, float* D_dev, int64_t* I_dev,
-                      void* ws_dev, size_t ws_bytes, void* stream) {
-    return knn_search_impl(packed_dev, sqnorm_dev, N, d, queries_dev, nq, k, metric, flags, id_offset, D_dev,
-                           I_dev, ws_dev, ws_bytes, stream, nullptr, nullptr);
+    const KnnOptions o = knn_options();
+    Plan p = plan_search(N, d, nq, k, metric, o);
+    if (p.route == ROUTE_ROW_RANGES) p = plan_search(p.part.per, d, nq, PART_K, metric, o);  // the scan of each row range
+    return p.route == ROUTE_SCREEN_STREAM ? MQ_SCAN_KIND_STREAM : p.route == ROUTE_SCREEN_TILE ? MQ_SCAN_KIND_TILE : MQ_SCAN_KIND_NONE;
 }
 
 int mq_knn_search_f32_ev(const float* packed_dev, const float* sqnorm_dev, int64_t N, int d, const float* queries_dev,
                          int nq, int k, int metric, int flags, int64_t id_offset, float* D_dev, int64_t* I_dev,
                          void* ws_dev, size_t ws_bytes, void* stream, void* ev_scan_begin, void* ev_scan_end) {
-    return knn_search_impl(packed_dev, sqnorm_dev, N, d, queries_dev, nq, k, metric, flags, id_offset, D_dev,
-                           I_dev, ws_dev, ws_bytes, stream, ev_scan_begin, ev_scan_end);
+    if (nq == 0) return MQ_OK;
+    const SearchCall c{packed_dev, sqnorm_dev, nullptr, nullptr, nullptr, N, d, queries_dev, nq, k, metric, flags, id_offset, D_dev, I_dev,
+                       (hipStream_t)stream, ev_scan_begin, ev_scan_end, dbg_ptr()};
+    Plan p;
+    if (const int rc = admit_search(c, false, ws_dev, ws_bytes, knn_options(), &p); rc != MQ_OK) return rc;
+    const Workspace w = workspace_view(p, ws_dev);
+    if (p.route != ROUTE_L2_DIRECT) return search_exact(c, p, w);
+    const float* q_rm;
+    if (const int rc = prepare_queries(c, w, true, &q_rm); rc != MQ_OK) return rc;
+    return search_l2_direct(c, p, w, q_rm);
+}
+
+int mq_knn_search_f32(const float* packed_dev, const float* sqnorm_dev, int64_t N, int d, const float* queries_dev,
+                      int nq, int k, int metric, int flags, int64_t id_offset, float* D_dev, int64_t* I_dev,
+                      void* ws_dev, size_t ws_bytes, void* stream) {
+    return mq_knn_search_f32_ev(packed_dev, sqnorm_dev, N, d, queries_dev, nq, k, metric, flags, id_offset, D_dev, I_dev, ws_dev,
+                                ws_bytes, stream, nullptr, nullptr);
 }
 
 /* ---- screened path (bf16 screening + exact re-scoring): see knn_screen.inc ---- */
 size_t mq_knn_screen_bytes(int64_t n_rows, int d, int metric) {
     return (size_t)mq_padded_rows(n_rows) * (size_t)screen_dp(d, metric) * 2;
-}
-
-// bf16 screening copy + error statistics of rows [row_offset, row_offset + n) of the row-major store
-static int screen_copy_and_stats(const float* sqnorm_dev, int d, int metric, int64_t row_offset, int64_t n, float* rowmajor_dev,
-                                 uint16_t* bf16_dev, float* xstats_dev, const float* center_dev, hipStream_t st) {
-    const int dp = screen_dp(d, metric);
-    const float* rm = rowmajor_dev + (size_t)row_offset * d;
-    const int64_t quads = n * (int64_t)(dp / 4);
-    if (metric == MQ_METRIC_IP_CENTRED)  // rows of x - c and their row term c . (x - c): 64 rows per workgroup
-        hipLaunchKernelGGL(to_bf16_rows_centred_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, rm, n, d, dp,
-                           (unsigned short*)bf16_dev, center_dev, row_offset);
-    else
-        hipLaunchKernelGGL(to_bf16_rows_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, rm, n, d, dp,
-                           (unsigned short*)bf16_dev, metric == MQ_METRIC_L2 ? 1 : 0, sqnorm_dev + row_offset, center_dev, row_offset);
-    MQ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(row_err_stats_kernel, dim3((unsigned)((n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048)), dim3(256), 0, st, rm,
-                       (const unsigned short*)bf16_dev, n, d, dp, (unsigned*)xstats_dev, center_dev, row_offset,
-                       metric == MQ_METRIC_L2 ? 1 : 0);
-    return mq_launch_status();
 }
 
 int mq_knn_screen_prepare(const float* packed_dev, const float* sqnorm_dev, int64_t capacity_rows, int d, int metric,
@@ -1579,208 +1826,48 @@ int mq_knn_search_screened_f32(const float* packed_dev, const float* sqnorm_dev,
                                int nq, int k, int metric, int flags, int64_t id_offset, float* D_dev, int64_t* I_dev,
                                void* ws_dev, size_t ws_bytes, void* stream, void* ev_scan_begin, void* ev_scan_end) {
     if (nq == 0) return MQ_OK;
-    if (!screen_metric_ok(metric)) return MQ_EINVAL;
-    if (flags & ~MQ_KNN_SCREENED_FLAGS) return MQ_EINVAL;
-    // the two halves of one search (MQ_KNN_FLAG_PHASE_*): neither or both bits = the whole search
+    const SearchCall c{packed_dev, sqnorm_dev, rowmajor_dev, bf16_dev, xstats_dev, N, d, queries_dev, nq, k, metric, flags, id_offset,
+                       D_dev, I_dev, (hipStream_t)stream, ev_scan_begin, ev_scan_end, nullptr};
+    const KnnOptions o = knn_options();
+    Plan p;
+    if (const int rc = admit_search(c, true, ws_dev, ws_bytes, o, &p); rc != MQ_OK) return rc;
+    const Workspace w = workspace_view(p, ws_dev);
+    // the two halves of one search (MQ_KNN_FLAG_PHASE_*): neither or both bits = the whole search.  A route the screen does not
+    // serve is one piece: the FRONT call does all of it, the TAIL call has nothing left to do
     const int phase = flags & (MQ_KNN_FLAG_PHASE_FRONT | MQ_KNN_FLAG_PHASE_TAIL);
     const bool do_front = phase != MQ_KNN_FLAG_PHASE_TAIL, do_tail = phase != MQ_KNN_FLAG_PHASE_FRONT;
-    const int l2norm_queries = query_l2norm_form(flags);
-    const unsigned flip = tie_flip(flags);
-    // MQ_METRIC_IP_CENTRED: the index was built for the centred-query screen (two extra columns = the row term c . (x - c), the
-    // centre itself behind the statistics: xstats_dev[4 .. 4 + d)); everything exact -- re-scoring, fallback scans, merges -- is
-    // the plain inner product
-    const int l2 = metric == MQ_METRIC_L2;
-    const int ipc = metric == MQ_METRIC_IP_CENTRED;
-    const int tm = true_metric(metric);
-    const int dp = screen_dp(d, metric);
-    // packed_dev may be NULL (an index that keeps no panel copy): the exact-scan fallback and FAISS's small-batch L2 form then
-    // read the row-major copy
-    const float* const X = packed_dev ? packed_dev : rowmajor_dev;
-    if (!sqnorm_dev || !rowmajor_dev || !bf16_dev || !xstats_dev || !queries_dev || !D_dev || !I_dev || !ws_dev)
-        return MQ_EINVAL;
-    if (N <= 0 || d <= 0 || nq < 0 || k <= 0) return MQ_EINVAL;
-    if (k > MQ_KNN_MAX_K) return MQ_EUNSUPPORTED;
-    if (N >= 0xFFFFFFFFll) return MQ_EUNSUPPORTED;
-    const Geometry g = geometry(N, d, nq, k, num_cus(), tm);
-    if (ws_bytes < g.total) return MQ_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    // searches served without the screen are one piece: the FRONT call does all of it, the TAIL call has nothing left to do
-    if ((l2 && nq < MQ_KNN_L2_DIRECT_BELOW) || k > SCREEN_MAX_K) {
-        if (!do_front) return MQ_OK;
+    const bool screen = p.route == ROUTE_SCREEN_STREAM || p.route == ROUTE_SCREEN_TILE;
+    if (!screen && !do_front) return MQ_OK;
+    const float* q_rm;
+    if (const int rc = prepare_queries(c, w, do_front, &q_rm); rc != MQ_OK) return rc;
+    switch (p.route) {
+        case ROUTE_L2_DIRECT: return search_l2_direct(c, p, w, q_rm);
+        case ROUTE_ROW_RANGES: return search_row_ranges(c, p, w, o, q_rm);
+        case ROUTE_EXACT_ROUNDS: return exact_fallback(c, p, w, q_rm, nullptr, PANELS_CLEAR_AND_PACK, c.ev0, c.ev1);
+        case ROUTE_SCREEN_STREAM:
+        case ROUTE_SCREEN_TILE:
+            if (do_front)
+                if (const int rc = screen_front(c, p, w, q_rm); rc != MQ_OK) return rc;
+            return do_tail ? screen_tail(c, p, w, q_rm) : MQ_OK;
     }
-    if (l2 && nq < MQ_KNN_L2_DIRECT_BELOW)
-        return knn_search_l2_direct(packed_dev, rowmajor_dev, N, d, queries_dev, nq, k, flags & MQ_KNN_ALL_FLAGS, id_offset, D_dev,
-                                    I_dev, ws_dev, g, st);
-    char* ws = (char*)ws_dev;
-    float* Qp = (float*)(ws + g.off_qp);
-    float* qn = (float*)(ws + g.off_qn);
-    float* qtmp = (float*)(ws + g.off_qtmp);
-    u64* pools = (u64*)(ws + g.off_lists);
-    unsigned short* Qb = (unsigned short*)(ws + g.off_qb);
-    float* margin = (float*)(ws + g.off_margin);
-    int* pcount = (int*)(ws + g.off_pcount);
-    int* ovf = (int*)(ws + g.off_ovf);
-    unsigned* cand = (unsigned*)(ws + g.off_cand);
-    u64* ckeys = (u64*)(ws + g.off_ckeys);
-    int* ccount = (int*)(ws + g.off_ccount);
-
-    // queries: optional "L2norm," transform applied ONCE in row-major form (so that the panel copy, the
-    // bf16 copy and the re-scoring all see the same fp32 values), then panel pack (+ ||q||^2) and bf16 copy
-    const float* q_rm = queries_dev;
-    if (l2norm_queries) {
-        if (do_front) {
-            MQ_HIP(hipMemcpyAsync(qtmp, queries_dev, (size_t)nq * d * 4, hipMemcpyDeviceToDevice, st));
-            launch_l2norm_rows(qtmp, (int64_t)nq, d, l2norm_queries, st);
-            MQ_HIP(hipGetLastError());
-        }
-        q_rm = qtmp;
-    }
-    if (const PartPlan pl = partition_plan(N, k); pl.P) {
-        // SCREEN_MAX_K < k <= 1792: P contiguous row ranges, each searched for its exact top-224 by this same function, then merged
-        // and proved (partition_merge_kernel); flagged query tiles are recomputed by the exact rounds below
-        char* extra = ws + g.total;
-        const size_t e = (size_t)pl.P * (size_t)nq * PART_K;
-        float* Dp = (float*)extra;
-        long long* Ip = (long long*)(extra + round_up((int64_t)(e * 4), 256));
-        int* pflags = (int*)((char*)Ip + round_up((int64_t)(e * 8), 256));
-        if (ws_bytes < g.total + partition_extra_bytes(N, nq, k)) return MQ_EWORKSPACE;
-        const int dpb = screen_dp(d, metric);
-        for (int p_ = 0; p_ < pl.P; ++p_) {
-            const int64_t r0 = (int64_t)p_ * pl.per, rows = r0 + pl.per <= N ? pl.per : N - r0;
-            const int rc = mq_knn_search_screened_f32(nullptr, sqnorm_dev + r0, rowmajor_dev + (size_t)r0 * d, bf16_dev + (size_t)r0 * dpb,
-                                                      xstats_dev, rows, d, queries_dev, nq, PART_K, metric, flags & MQ_KNN_ALL_FLAGS, r0,
-                                                      Dp + (size_t)p_ * nq * PART_K, (int64_t*)Ip + (size_t)p_ * nq * PART_K, ws_dev,
-                                                      g.total, stream, p_ == 0 ? ev_scan_begin : nullptr,
-                                                      p_ == pl.P - 1 ? ev_scan_end : nullptr);
-            if (rc != MQ_OK) return rc;
-        }
-        MQ_HIP(hipMemsetAsync(pflags, 0, (size_t)g.nqt * 4, st));
-        hipLaunchKernelGGL(partition_merge_kernel, dim3((unsigned)nq), dim3(256), 0, st, Dp, Ip, pl.P, nq, k, l2, flip, (long long)id_offset,
-                           (long long)pl.per, (long long)N, D_dev, (long long*)I_dev, pflags);
-        MQ_HIP(hipGetLastError());
-        // flagged tiles: the exact rounds (no-op otherwise: every workgroup of an unflagged tile returns at once)
-        if (const int rc = pack_query_panels(g, q_rm, nq, d, 0, pflags, true, Qp, qn, st); rc != MQ_OK) return rc;
-        return exact_scan_rounds(tm, packed_dev == nullptr, exact_scan_args(g, X, sqnorm_dev, Qp, qn, pools, N, d, k, flip, pflags, nullptr),
-                                 g, nq, k, id_offset, D_dev, I_dev, ws, pflags, st, nullptr, nullptr);
-    }
-    if (k > SCREEN_MAX_K) {
-        // More than SCREEN_MAX_K neighbours: the bounded screening buffers are sized for the reference's k = 100 (the pools hold
-        // 512 survivors per slab, the stripe bound works on 256 slots: k <= 224 still goes through the screen, round 3); the exact
-        // scan serves the call in ceil(k / 128) rounds (from the panel copy, or from the row-major copy of an index without one).
-        if (const int rc = pack_query_panels(g, q_rm, nq, d, 0, nullptr, true, Qp, qn, st); rc != MQ_OK) return rc;
-        return exact_scan_rounds(tm, packed_dev == nullptr, exact_scan_args(g, X, sqnorm_dev, Qp, qn, pools, N, d, k, flip, nullptr, nullptr),
-                                 g, nq, k, id_offset, D_dev, I_dev, ws, nullptr, st, ev_scan_begin, ev_scan_end);
-    }
-    if (do_front) {
-    // The fp32 panel copy of the queries (+ ||q||^2) serves the exact-scan fallback -- and, for the L2 metric, the
-    // re-scoring (||q||^2).  With the inner product it is made after the screened pipeline, for flagged tiles only.
-    if (l2) {
-        const int rc = pack_query_panels(g, q_rm, nq, d, 0, nullptr, true, Qp, qn, st);
-        if (rc != MQ_OK) return rc;
-    }
-    if (g.nqpad > nq)  // bf16 rows of the padding queries: the last tile (tile layout: its real rows are written below)
-        MQ_HIP(hipMemsetAsync(Qb + (size_t)(g.nqpad - TQ) * dp, 0, (size_t)TQ * dp * 2, st));
-    {
-        const int64_t quads = (int64_t)nq * (dp / 4);
-        hipLaunchKernelGGL(to_bf16_rows_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, q_rm, (int64_t)nq, d, dp, Qb,
-                           (l2 || ipc) ? 2 : 0, (const float*)nullptr, ipc ? xstats_dev + 4 : (const float*)nullptr, (int64_t)0);
-        MQ_HIP(hipGetLastError());
-        hipLaunchKernelGGL(screen_margin_kernel, dim3((unsigned)((g.nqpad + 3) / 4)), dim3(256), 0, st, q_rm, Qb, xstats_dev, nq,
-                           (int)g.nqpad, d, dp, margin, l2 ? 1 : (ipc ? 2 : 0), ipc ? xstats_dev + 4 : (const float*)nullptr,
-                           (unsigned*)ovf, (g.off_smax + (size_t)g.nqpad * g.ms * 4 - g.off_ovf) / 4);  // clears ovf + gthr + smax
-        MQ_HIP(hipGetLastError());
-    }
-    // 1. bf16 screening scan
-    {
-        ScreenArgs a;
-        a.Xb = bf16_dev; a.Qb = Qb; a.margin = margin; a.pools = pools; a.pcount = pcount; a.ovf = ovf; a.gthr = (unsigned*)(ws + g.off_gthr);
-        a.smax = (unsigned*)(ws + g.off_smax); a.ms = g.ms; a.sps = g.sps;
-        a.dbg = dbg_ptr();
-        a.N = N; a.dp = dp; a.nqt = g.nqt; a.S = g.S; a.k = k; a.qpx = g.qpx_screen; a.nchunks = g.nchunks;
-        if (ev_scan_begin) MQ_HIP(hipEventRecord((hipEvent_t)ev_scan_begin, st));
-        int small_nkb = 0;
-        bool small_rowterm = false;
-        if (small_scan_serves(g, N, d, metric, k, &small_nkb, &small_rowterm)) {
-            // one query tile: the streaming kernel with the queries in registers (knn_small8.inc)
-            SmallArgs sa;
-            sa.s = a;
-            sa.ntiles = (N + SM_ROWS - 1) / SM_ROWS;
-            sa.rowterm = small_rowterm ? 1 : 0;
-            sa.sqn = (small_rowterm && metric == MQ_METRIC_L2) ? sqnorm_dev : nullptr;
-            sa.nkb_copy = dp / SBK;
-            const int rc = launch_small_scan(sa, small_nkb, g.S, st);
-            if (rc != MQ_OK) return rc;
-        } else if (knn_opt(MQ_KNN_OPT_SCAN_MFMA)) {  // the tile kernel on 16x16x32 MFMAs
-            MQ_DYNAMIC_LDS(S_LDS_TOTAL, screen_scan16_kernel);
-            hipLaunchKernelGGL(screen_scan16_kernel, dim3((unsigned)(g.nqt * g.S)), dim3(1024), S_LDS_TOTAL, st, a);
-        } else {  // ... on 32x32x16 MFMAs
-            MQ_DYNAMIC_LDS(S_LDS_TOTAL, screen_scan_kernel);
-            hipLaunchKernelGGL(screen_scan_kernel, dim3((unsigned)(g.nqt * g.S)), dim3(1024), S_LDS_TOTAL, st, a);
-        }
-        MQ_HIP(hipGetLastError());
-        if (ev_scan_end) MQ_HIP(hipEventRecord((hipEvent_t)ev_scan_end, st));
-    }
-    }  // do_front
-    if (!do_tail) return MQ_OK;
-    // 2.-4. candidates -> exact scores -> exact top-k
-#ifdef MQ_TIMING
-    {
-        unsigned long long* p = dbg_ptr();
-        MQ_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_cs_dbg), &p, sizeof(p)));
-    }
-#endif
-    {
-        const int* layout_word = g.nqt == 1 ? (const int*)(ovf + 1) : (const int*)nullptr;
-        const unsigned* gthr = (const unsigned*)(ws + g.off_gthr);
-        const unsigned* smax = (const unsigned*)(ws + g.off_smax);
-        // (the walk is checked against the word the scan left)
-        const int walk = small_scan_serves(g, N, d, metric, k) ? CSEL_WALK_HALVES : (g.S >= 64 ? CSEL_WALK_SLICE_LINES : CSEL_WALK_SLICES);
-        const auto csel = walk == CSEL_WALK_HALVES ? cand_select_kernel<CSEL_WALK_HALVES>
-                          : walk == CSEL_WALK_SLICE_LINES ? cand_select_kernel<CSEL_WALK_SLICE_LINES> : cand_select_kernel<CSEL_WALK_SLICES>;
-        hipLaunchKernelGGL(csel, dim3((unsigned)nq), dim3(256), 0, st, pools, pcount, margin, gthr, smax, g.ms, ovf, nq, g.S, k, cand,
-                           ccount, layout_word);
-    }
-    MQ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)nq, RMAX / 64), dim3(256), 0, st, rowmajor_dev, q_rm, d, cand, ccount, ckeys,
-                       l2 ? (const float*)qn : (const float*)nullptr, sqnorm_dev, flip);
-    MQ_HIP(hipGetLastError());
-    if (k <= KF)
-        hipLaunchKernelGGL(final_select_kernel<128>, dim3((unsigned)nq), dim3(64), 0, st, ckeys, ccount, ovf, k, (long long)id_offset,
-                           D_dev, (long long*)I_dev, l2, flip);
-    else
-        hipLaunchKernelGGL(final_select_kernel<FINAL_SORT_KEYS>, dim3((unsigned)nq), dim3(64), 0, st, ckeys, ccount, ovf, k,
-                           (long long)id_offset, D_dev, (long long*)I_dev, l2, flip);
-    MQ_HIP(hipGetLastError());
-    // 5. query tiles whose bounded buffers overflowed are recomputed by the exact scan (no-op otherwise:
-    //    every workgroup of an unflagged tile returns at once)
-    {
-        if (!l2) {  // (the L2 panels were made in front of the screen)
-            const int rc = pack_query_panels(g, q_rm, nq, d, 0, ovf, false, Qp, qn, st);
-            if (rc != MQ_OK) return rc;
-        }
-        const int rc = exact_scan_rounds(tm, packed_dev == nullptr, exact_scan_args(g, X, sqnorm_dev, Qp, qn, pools, N, d, k, flip, ovf, nullptr),
-                                         g, nq, k, id_offset, D_dev, I_dev, ws, ovf, st, nullptr, nullptr);
-        if (rc != MQ_OK) return rc;
-    }
-    return MQ_OK;
+    return MQ_EINVAL;  // (not reached: every route returns above)
 }
 
 /* Debug/telemetry of the last screened search held in `ws_dev`: out[0] = flagged query tiles,
  * out[1] = total candidates re-scored, out[2] = max candidates of one query.  Synchronises the stream. */
 int mq_knn_screen_stats(int64_t N, int d, int nq, int k, const void* ws_dev, int64_t out[8], void* stream) {
     if (!ws_dev || !out || nq <= 0) return MQ_EINVAL;
-    const Geometry g = geometry(N, d, nq, k, num_cus());  // the offsets read here do not depend on the metric
+    const Plan p = plan_search(N, d, nq, k, -1, knn_options());  // the regions read here do not depend on the metric
+    const Geometry& g = p.g;
+    const Workspace w = workspace_view(p, const_cast<void*>(ws_dev));
     MQ_HIP(hipStreamSynchronize((hipStream_t)stream));
     const size_t npc = (size_t)g.nqt * g.S * TQ * NSL;
-    int* ovf = (int*)malloc((size_t)g.nqt * 4);
-    int* cc = (int*)malloc((size_t)nq * 4);
-    int* pc = (int*)malloc(npc * 4);
-    float* mg = (float*)malloc((size_t)nq * 4);
-    if (!ovf || !cc || !pc || !mg) { free(ovf); free(cc); free(pc); free(mg); return MQ_EINVAL; }
-    hipError_t e1 = hipMemcpy(ovf, (const char*)ws_dev + g.off_ovf, (size_t)g.nqt * 4, hipMemcpyDeviceToHost);
-    hipError_t e2 = hipMemcpy(cc, (const char*)ws_dev + g.off_ccount, (size_t)nq * 4, hipMemcpyDeviceToHost);
-    hipError_t e3 = hipMemcpy(pc, (const char*)ws_dev + g.off_pcount, npc * 4, hipMemcpyDeviceToHost);
-    hipError_t e4 = hipMemcpy(mg, (const char*)ws_dev + g.off_margin, (size_t)nq * 4, hipMemcpyDeviceToHost);
+    std::vector<int> ovf((size_t)g.nqt), cc((size_t)nq), pc(npc);
+    std::vector<float> mg((size_t)nq);
+    MQ_HIP(hipMemcpy(ovf.data(), w.ovf, ovf.size() * 4, hipMemcpyDeviceToHost));
+    MQ_HIP(hipMemcpy(cc.data(), w.ccount, cc.size() * 4, hipMemcpyDeviceToHost));
+    MQ_HIP(hipMemcpy(pc.data(), w.pcount, pc.size() * 4, hipMemcpyDeviceToHost));
+    MQ_HIP(hipMemcpy(mg.data(), w.margin, mg.size() * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; ++i) out[i] = 0;
     for (int i = 0; i < g.nqt; ++i) out[0] += ovf[i] != 0;
     for (int i = 0; i < nq; ++i) { out[1] += cc[i]; if (cc[i] > out[2]) out[2] = cc[i]; }
@@ -1794,37 +1881,7 @@ int mq_knn_screen_stats(int64_t N, int d, int nq, int k, const void* ws_dev, int
     for (int i = 0; i < nq; ++i) if (mg[i] > mm || mg[i] != mg[i]) mm = mg[i];
     out[5] = mm < 9e12f ? (int64_t)(mm * 1e6f) : INT64_MAX;  /* max margin in 1e-6 units (INT64_MAX: infinite) */
     out[6] = g.S;
-    free(ovf); free(cc); free(pc); free(mg);
-    MQ_HIP(e1);
-    MQ_HIP(e2);
-    MQ_HIP(e3);
-    MQ_HIP(e4);
     return MQ_OK;
-}
-
-static int topk_merge_impl(const float* Ds_dev, const int64_t* Is_dev, size_t d_stride, size_t i_stride, int nshards, int nq,
-                           int k, int metric_and_tie, float* D_dev, int64_t* I_dev, void* stream) {
-    if (nq == 0) return MQ_OK;
-    if (!Ds_dev || !Is_dev || !D_dev || !I_dev || nshards <= 0 || nq < 0 || k <= 0) return MQ_EINVAL;
-    const bool desc = (metric_and_tie & MQ_MERGE_TIE_ID_DESC) != 0;
-    const int metric = metric_and_tie & ~MQ_MERGE_TIE_ID_DESC;
-    if (metric != MQ_METRIC_IP && metric != MQ_METRIC_L2) return MQ_EINVAL;
-    if (k > MQ_KNN_MAX_K) return MQ_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (k > KF) {
-        if (metric == MQ_METRIC_IP)
-            hipLaunchKernelGGL(shard_merge_big_kernel<MQ_METRIC_IP>, dim3((unsigned)nq), dim3(256), 0, st, Ds_dev, (const long long*)Is_dev,
-                               d_stride, i_stride, nshards, nq, k, D_dev, (long long*)I_dev, desc);
-        else
-            hipLaunchKernelGGL(shard_merge_big_kernel<MQ_METRIC_L2>, dim3((unsigned)nq), dim3(256), 0, st, Ds_dev, (const long long*)Is_dev,
-                               d_stride, i_stride, nshards, nq, k, D_dev, (long long*)I_dev, desc);
-    } else if (metric == MQ_METRIC_IP)
-        hipLaunchKernelGGL(shard_merge_kernel<MQ_METRIC_IP>, dim3((unsigned)nq), dim3(128), 0, st, Ds_dev,
-                           (const long long*)Is_dev, d_stride, i_stride, nshards, nq, k, D_dev, (long long*)I_dev, desc);
-    else
-        hipLaunchKernelGGL(shard_merge_kernel<MQ_METRIC_L2>, dim3((unsigned)nq), dim3(128), 0, st, Ds_dev,
-                           (const long long*)Is_dev, d_stride, i_stride, nshards, nq, k, D_dev, (long long*)I_dev, desc);
-    return mq_launch_status();
 }
 
 int mq_topk_merge_f32(const float* Ds_dev, const int64_t* Is_dev, int nshards, int nq, int k, int metric, float* D_dev,
