@@ -141,6 +141,161 @@ def test_rank_metrics_equal_the_restatement(nq, k, n_docs):
         M.evaluate(qrels, run, ["ndcg@10"])
 
 
+WIDE_NAMES = ["mrr@100", "mrr@1", "mrr", "precision@1", "precision@20", "precision", "hit_rate@20", "hit_rate@3", "recall@10", "recall",
+              "precision@1000", "mrr@63", "mrr@64", "hit_rate@65", "recall@127", "precision@128"]
+
+
+def _ballot_edge_rows(k):
+    """Rows for a width-k table as (run, qrels, [(length, position of the ONE relevant document | None)]): lengths 0, k, 64, 128,
+    63, 65, 1 (as far as k allows), the relevant document at 63, 64, 127 (last and first lane of a 64-lane ballot) or at the row's
+    end where it is shorter; then a few random rows, and two rows whose every document is judged (hits in every ballot)."""
+    rng = np.random.default_rng(k)
+    rows = [(0, None), (k, 63), (k, 64), (k, 127), (64, 63), (128, 127), (128, 64), (63, 62), (65, 64), (1, 0)]
+    rows += [(int(n), int(rng.integers(0, n))) for n in rng.integers(1, k + 1, 4)]
+    rows = [(n, None if at is None else min(at, n - 1)) for n, at in rows if n <= k] + [(0, None)]
+    run, qrels = {}, {}
+    for q, (n, at) in enumerate(rows + [(k, "all"), (k // 2, "all")]):
+        docs = [str(int(d)) for d in rng.permutation(5000)[:n]]
+        run[f"q{q}"] = {d: float(n - i) for i, d in enumerate(docs)}
+        if at == "all":
+            qrels[f"q{q}"] = {d: int(rng.integers(0, 3)) for d in docs}
+        else:
+            qrels[f"q{q}"] = {"9999": 1} if at is None else {docs[at]: 1, "9999": 1}     # 9999: in no run
+    return run, qrels, rows
+
+
+@pytest.mark.parametrize("k", [63, 64, 65, 128, 192])
+def test_rank_metrics_at_the_ballot_boundaries(k):
+    """run_metrics_kernel reads a row 64 ids at a time: rows that end exactly on a ballot, one before and one after it, empty rows,
+    and the only relevant document on the last lane of a ballot or the first lane of the next.  Sixteen metrics in one call."""
+    from oracle import fuse as ofuse
+    from viquae_amd.ir import metrics as M
+    from viquae_amd.ir.runs import ArrayRun
+    run, qrels, rows = _ballot_edge_rows(k)
+    lengths = [n for n, _ in rows]
+    assert len(WIDE_NAMES) == M.MAX_METRICS == 16 and 0 in lengths and (k, min(63, k - 1)) in rows
+    assert k < 64 or (64, 63) in rows
+    assert k < 65 or (k, 64) in rows
+    assert k < 128 or ((128, 127) in rows and (k, 127) in rows)
+    got, per_q = M.evaluate(qrels, run, WIDE_NAMES, return_per_query=True)
+    for name in WIDE_NAMES:
+        want, values = ofuse.rank_metric(run, qrels, name)
+        assert np.array_equal(per_q[name], np.array(values)), name
+        assert got[name] == want, name
+    for q, (n, at) in enumerate(rows):                # by hand: the planted document alone decides these
+        rr = 0.0 if at is None else 1.0 / (at + 1)
+        assert per_q["mrr"][q] == rr and per_q["mrr@64"][q] == (rr if at is not None and at < 64 else 0.0), (q, n, at)
+        assert per_q["mrr@63"][q] == (rr if at is not None and at < 63 else 0.0), (q, n, at)
+        assert per_q["recall@127"][q] == (0.5 if at is not None and at < 127 else 0.0), (q, n, at)
+    ids = np.full((len(run), k), -1, dtype=np.int64)
+    for q, results in enumerate(run.values()):
+        ids[q, :len(results)] = [int(d) for d in results]
+    arr = ArrayRun()
+    arr.add_block(list(run), ids, np.zeros(ids.shape, dtype=np.float32))
+    assert M.evaluate(qrels, arr, WIDE_NAMES) == got
+    with pytest.raises(ValueError):
+        M.evaluate(qrels, run, WIDE_NAMES + ["recall@1"])           # seventeen
+
+
+def test_rank_metrics_row_ends_at_its_first_negative_id(hip_lib):
+    """The C entry itself (ArrayRun.tables clears what follows a negative id before the device sees it): ids after the first
+    negative id of a row are not part of it, wherever in the 64-lane ballots that id sits."""
+    import ctypes
+    from oracle import fuse as ofuse
+    from viquae_amd.ir import metrics as M
+    K, dev = 130, "cuda:0"
+    rows = np.arange(6 * K, dtype=np.int64).reshape(6, K) + 100
+    rows[0, :3] = [5, -1, 7]            # relevant 7 after the end
+    rows[1, 63] = -1                    # last lane of the first ballot
+    rows[2, 64] = -1                    # first lane of the second
+    rows[3, 0] = -1                     # an empty row with ids behind it
+    rows[4, 70], rows[4, 100] = -1, -1  # two negative ids: the first one counts
+    rel = [[5, 7], [int(rows[1, 62]), int(rows[1, 64])], [int(rows[2, 63]), int(rows[2, 65])], [int(rows[3, 1])],
+           [int(rows[4, 69]), int(rows[4, 71]), int(rows[4, 101])], [int(rows[5, 129])]]
+    run, qrels = {}, {}
+    for q in range(6):
+        neg = np.flatnonzero(rows[q] < 0)
+        n = int(neg[0]) if neg.size else K
+        run[f"q{q}"] = {str(int(d)): 0.0 for d in rows[q, :n]}
+        qrels[f"q{q}"] = {str(d): 1 for d in rel[q]}
+    assert [len(r) for r in run.values()] == [1, 63, 64, 0, 70, 130]
+    names = ["mrr", "precision", "precision@100", "hit_rate@128", "recall", "recall@64", "mrr@1"]
+    parsed = [M.parse_metric(n) for n in names]
+    ptr = np.cumsum([0] + [len(r) for r in rel]).astype(np.int64)
+    rel_ids = np.concatenate([np.sort(np.array(r, dtype=np.int64)) for r in rel])
+    ids_d, ptr_d, rel_d = [torch.from_numpy(x).to(dev) for x in (rows, ptr, rel_ids)]
+    per_q = torch.empty((len(names), 6), dtype=torch.float64, device=dev)
+    mean = torch.empty((len(names),), dtype=torch.float64, device=dev)
+    codes = (ctypes.c_int * len(names))(*[c for c, _ in parsed])
+    ks = (ctypes.c_int * len(names))(*[k for _, k in parsed])
+    assert hip_lib.mq_run_metrics_f64(ids_d.data_ptr(), 6, K, ptr_d.data_ptr(), rel_d.data_ptr(), len(names), codes, ks,
+                                      per_q.data_ptr(), mean.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    for i, name in enumerate(names):
+        want, values = ofuse.rank_metric(run, qrels, name)
+        assert per_q[i].tolist() == values, name
+        assert mean[i].item() == want, name
+    assert per_q[0].tolist() == [1.0, 1.0 / 63, 1.0 / 64, 0.0, 1.0 / 70, 1.0 / 130]     # mrr: by hand
+    # seventeen metrics: refused before anything is launched
+    codes17, ks17 = (ctypes.c_int * 17)(*([0] * 17)), (ctypes.c_int * 17)(*([0] * 17))
+    assert hip_lib.mq_run_metrics_f64(ids_d.data_ptr(), 6, K, ptr_d.data_ptr(), rel_d.data_ptr(), 17, codes17, ks17,
+                                      per_q.data_ptr(), mean.data_ptr(), None) == -1
+
+
+MEAN_NAMES = ["mrr", "mrr@3", "precision@3", "precision@7", "precision", "recall", "recall@10", "recall@5", "recall@3", "precision@20",
+              "recall@15", "precision@11", "precision@13", "recall@7", "mrr@2", "recall@20"]
+
+
+def _pairwise_sum(a, split_on_8=True):
+    """numpy's pairwise summation restated (blocks of <= 128 with eight accumulators, halves split on a multiple of 8);
+    split_on_8=False is the plausible WRONG restatement that halves at n // 2."""
+    n = len(a)
+    if n < 8:
+        res = 0.0
+        for x in a:
+            res += x
+        return res
+    if n <= 128:
+        r = [float(x) for x in a[:8]]
+        i = 8
+        while i < n - n % 8:
+            for j in range(8):
+                r[j] += a[i + j]
+            i += 8
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+        for x in a[i:]:
+            res += x
+        return res
+    h = n // 2
+    if split_on_8:
+        h -= h % 8
+    return _pairwise_sum(a[:h], split_on_8) + _pairwise_sum(a[h:], split_on_8)
+
+
+@pytest.mark.parametrize("nq", [7, 8, 9, 127, 128, 129, 136, 255, 256, 257, 264, 1023, 1024, 1025, 2049])
+def test_metric_mean_is_numpy_pairwise_mean(nq):
+    """np_mean_rows_kernel restates numpy's pairwise summation: the plain loop below 8, the eight-accumulator block up to 128,
+    halves split on a multiple of 8 above.  Metric values such as 1 / r are not dyadic, so another summation order changes the
+    bits: the test proves on the host that, for its own vectors, a plain loop (nq >= 127) and a split at n // 2 (the nq at which
+    that differs: 136, 255, 264, 1023) give another sum for at least one of the sixteen metrics."""
+    from oracle import fuse as ofuse
+    from viquae_amd.ir import metrics as M
+    run = _random_runs(nq, nq, 1, 20, 60, empty_every=9)[0]
+    qrels = _random_qrels(nq + 1, nq, 60, dense=0.6)
+    got, per_q = M.evaluate(qrels, run, MEAN_NAMES, return_per_query=True)
+    plain_differs = halves_differ = False
+    for name in MEAN_NAMES:
+        want, values = ofuse.rank_metric(run, qrels, name)
+        assert np.array_equal(per_q[name], np.array(values)), name
+        assert got[name] == float(np.mean(per_q[name])), name          # bit for bit
+        assert got[name] == want, name
+        assert _pairwise_sum(values) / nq == want, name                # the restatement above is numpy's
+        plain_differs |= sum(values) != _pairwise_sum(values)
+        halves_differ |= _pairwise_sum(values, split_on_8=False) != _pairwise_sum(values)
+    assert plain_differs or nq < 127
+    assert halves_differ == (nq in (136, 255, 264, 1023))
+
+
 def test_rank_metrics_with_named_documents_and_report_files(tmp_path):
     from oracle import fuse as ofuse
     from viquae_amd.ir import metrics as M

@@ -145,3 +145,61 @@ def test_fusion_class_like_dataset_search(tmp_path):
     assert_same_run(fused, case["unpinned_wsum_gzmuv_defmin"])
     with open(tmp_path / "test_run.json") as file:
         assert_same_run(json.load(file), case["unpinned_wsum_gzmuv_defmin"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# shapes and edges of mq_fuse_wsum_f64 that the cases above do not reach (tests/fuse_cases.py holds the shared cases)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nq", [1100, 2049])
+def test_more_queries_than_the_moments_kernel_has_threads(nq):
+    """fuse_moments_kernel strides over the queries by its 1024 threads: two and three steps, the default-minimum fill counted in
+    closed form, some (run, query) pairs empty.  A pool of 7 documents makes the unions overlap."""
+    runs = random_runs(nq, nq, 2, 3, 7, empty_every=5)
+    for norm in (None, "gzmuv", "zmuv"):
+        for defmin in (False, True):
+            want = ofuse.fusion_test(runs, [0.7, 0.3], norm=norm, defmin=defmin)
+            got = hfuse.fuse_runs(runs, [0.7, 0.3], norm=norm, defmin=defmin)
+            assert_same_run(got, want, exact=norm is None)
+
+
+@pytest.mark.parametrize("norm", [None, "gzmuv", "zmuv"])
+@pytest.mark.parametrize("defmin", [False, True])
+def test_hollow_case(norm, defmin):
+    """A run without any result (its gzmuv moments have no entry to average) and a query that is empty in every run."""
+    from tests import fuse_cases as fc
+    runs, _, _ = fc.case_data("hollow")
+    weights = [0.5, 0.25, 0.25]
+    want = fc.reference_fused(runs, [weights], norm, defmin)[0]
+    assert want["q3"] == {} and all(not results for results in runs[1].values())
+    assert_same_run(hfuse.fuse_runs(runs, weights, norm=norm, defmin=defmin), want, exact=norm is None)
+    q_ids, _, ids, scores = hfuse.runs_to_tables(runs)
+    out_ids, out_scores, counts = hfuse.fuse_tables(ids, scores, weights, norm=norm, defmin=defmin)
+    q = q_ids.index("q3")
+    assert counts[q].item() == 0
+    assert (out_ids[q] == -1).all().item() and (out_scores[q] == 0.0).all().item() and out_ids.shape[1] == 3 * 20
+    assert counts.tolist() == [len(want[q_id]) for q_id in q_ids]
+
+
+def test_id_edge_case():
+    """Ids 2^58 - 1, 2^58 - 2 and 0 in runs 0 and 31: the sort key (id << 5) | run at both ends of both fields.  Scores and weights
+    are dyadic, so the fused scores below are exact and the order is stated by hand."""
+    from tests import fuse_cases as fc
+    runs, _, _ = fc.case_data("id_edge")
+    b, b1 = str(2 ** 58 - 1), str(2 ** 58 - 2)
+    weights = [1.0] * 32
+    weights[7], weights[31] = 2.0, 0.5
+    got = hfuse.fuse_runs(runs, weights, norm=None, defmin=False)
+    assert list(got["q0"].items()) == [(b, 4.25), (b1, 3.5), ("0", 3.25), ("7", 0.25), ("5", 0.125)]
+    assert list(got["q1"].items()) == [(b, 1.5), ("0", 1.0), (b1, 1.0)]                 # equal scores: ascending id
+    assert_same_run(got, ofuse.fusion_test(runs, weights, norm=None, defmin=False), exact=True)
+    got = hfuse.fuse_runs(runs, weights, norm=None, defmin=True)
+    # q0: run 0 fills 5 and 7 with 1.0, run 7 (weight 2) fills b, b1 and 5 with 0.125, run 31 (weight 0.5) fills 7 with 0.25
+    assert list(got["q0"].items()) == [(b, 4.5), (b1, 3.75), ("0", 3.25), ("5", 1.375), ("7", 1.375)]
+    assert list(got["q1"].items()) == [(b1, 2.0), ("0", 1.5), (b, 1.5)]                 # run 7 is empty here: it fills nothing
+    assert_same_run(got, ofuse.fusion_test(runs, weights, norm=None, defmin=True), exact=True)
+    for norm in ("gzmuv", "zmuv"):
+        for defmin in (False, True):
+            want = fc.reference_fused(runs, [weights], norm, defmin)[0]
+            assert_same_run(hfuse.fuse_runs(runs, weights, norm=norm, defmin=defmin), want)
+    with pytest.raises(ValueError):
+        hfuse.fuse_runs([{"q": {str(2 ** 58): 1.0}}, {"q": {"1": 1.0}}], [1.0, 1.0], norm=None)

@@ -79,8 +79,8 @@ def _as_dict(run):
 
 def runs_to_tables(runs, device="cuda:0"):
     """``[{q_id: {doc_id: score}}]`` -> ``(q_ids, doc_names, ids, scores)`` with ids / scores ``[n_runs, nq, K]`` on
-    ``device``.  Document ids that are all decimal strings keep their integer value; otherwise they are numbered
-    in sorted order and ``doc_names`` holds the inverse."""
+    ``device``.  Document ids that are all decimal strings keep their integer value (below 2^58: ``ValueError`` otherwise);
+    otherwise they are numbered in sorted order and ``doc_names`` holds the inverse."""
     q_ids = list(runs[0].keys())
     for run in runs[1:]:
         if run.keys() != runs[0].keys():
@@ -106,6 +106,8 @@ def runs_to_tables(runs, device="cuda:0"):
     doc_names = None
     if numeric:
         to_int = int
+        if any(int(d) >= 1 << 58 for d in docs):   # the sort key is (id << 5) | run (include/meerqat_hip.h: 0 <= id < 2^58)
+            raise ValueError("document ids must be below 2^58")
     else:
         doc_names = sorted(docs, key=str)
         lookup = {d: i for i, d in enumerate(doc_names)}
